@@ -16,6 +16,13 @@ the counting kernel (art_count_device), which tests/test_parity_gpu.py checks ag
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 the driver uses
 torch.distributed.run (one process per GPU, MASTER_ADDR=127.0.0.1).
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step and the workload's description). --full adds everything else the line can carry, each
+measured in runs of its own after the timed region: per-kernel and roofline figures, the host-API
+p50 frame latency, the dynamic-scene step, the all-gather's own time and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (the arrays a caller of the timed path
+receives) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -91,9 +98,58 @@ def parse():
     p.add_argument("--dirs-count", type=int, default=1 << 24, help="directions per launch (dirs path)")
     p.add_argument("--dsp-frames", type=int, default=1024, help="frames per OnAudioFilterRead buffer (dsp path)")
     p.add_argument("--dsp-batch", type=int, default=65536, help="sources of the large-batch roofline run (dsp path)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need, after the timed steps: per-kernel "
+                        "and roofline figures, p50 host-API frame latency, the dynamic-scene step, the all-gather's "
+                        "own time, the CPU baseline (a plain run only times the steps)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the arrays the last timed step computed as DIR/<name>.npy "
+                        "(float32 / float64; at most 64 MB in all, larger arrays as a fixed seeded sample of rows)")
     p.add_argument("--dsp-sort", action="store_true",
                    help="group the device batch by filter class, as art_dsp_process does (dsp path)")
     return p.parse_args()
+
+
+DUMP_CAP_BYTES = 63 * 10 ** 6  # array bytes; the .npy headers fit in the last of the 64 MB
+
+
+def fan_output_arrays(out):
+    """FanOutputs -> {name: float array}: half bits as the float32 values they encode, counts and ids
+    as float32 / float64 (exact), struct fields one array each."""
+    arrs = {"echo": out.echo.view(np.float16).astype(np.float32), "muffle": out.muffle.astype(np.float32),
+            "perm": out.perm.astype(np.float32)}
+    for f in out.settings.dtype.names:
+        arrs[f"settings_{f}"] = np.ascontiguousarray(out.settings[f]).astype(np.float32)
+    if out.dsp is not None:
+        for f in out.dsp.dtype.names:
+            arrs[f"dsp_{f}"] = np.ascontiguousarray(out.dsp[f]).astype(np.float32)
+    if out.hit_points is not None:
+        arrs["hit_points"] = out.hit_points.view(np.float16).astype(np.float32)
+        arrs["hit_counts"] = out.hit_counts.astype(np.float32)
+        arrs["hit_ids"] = out.hit_ids.astype(np.float64)
+    return arrs
+
+
+def fan_block_arrays(block, lay, S, cfg, dsp):
+    """Packed per-fan result blocks (uint8 tensor, include/art_device.h art_fan_layout) -> named arrays."""
+    b = block[: S * lay["stride"]].cpu().numpy()
+    return fan_output_arrays(art.unpack_block(b, lay, S, cfg.R, cfg.H, cfg.T, 1, dsp=dsp))
+
+
+def write_outputs(dirpath, arrays):
+    """DIR/<name>.npy per array, float32 or float64. Above DUMP_CAP_BYTES in all, every array keeps the
+    same fixed, seeded sample of its rows (axis 0) and <name>_rows.npy holds the rows kept."""
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    sampled = sum(a.nbytes + 8 * a.shape[0] for a in arrays.values())  # with each row's float64 index
+    for name, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        if total > DUMP_CAP_BYTES:
+            keep = max(1, int(arr.shape[0] * DUMP_CAP_BYTES / sampled))
+            rows = np.sort(np.random.default_rng(0).choice(arr.shape[0], keep, replace=False))
+            np.save(os.path.join(dirpath, f"{name}_rows.npy"), rows.astype(np.float64))
+            arr = arr[rows]
+        np.save(os.path.join(dirpath, f"{name}.npy"), np.ascontiguousarray(arr))
 
 
 def host_cpu_info():
@@ -253,6 +309,33 @@ def main_dsp(a):
     if rank != 0:
         dist.destroy_process_group()
         return
+    if a.dump_outputs:  # the buffers art_dsp_process_device filtered in place, and the filter state it carries
+        write_outputs(a.dump_outputs, {"data": d_data.cpu().numpy(),
+                                       "state": d_state.cpu().numpy().view(np.float32).reshape(S, -1)})
+    value = frames_all / dt
+    res = {
+        "metric": "spatializer DSP stereo frames/s (per-sample OnAudioFilterRead chain)",
+        "value": value,
+        "unit": "stereo frames/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": dt / a.steps * 1e3,
+        "realtime_sources_at_48k": value / sr,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"dsp tick: {S} spatializers (config{cfg.index} sources) x {F} stereo frames @ 48 kHz",
+                   "sources_per_gpu": S, "frames": F, "grouped_by_filter_class": bool(a.dsp_sort), "parallelism": f"source-sharded x{world} (replicas, no collective)"},
+        "full": bool(a.full),
+    }
+    if not a.full:
+        print(json.dumps(res))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # host API (art_dsp_process): host buffers, H2D + kernel + D2H, per tick
     import ctypes as C
     c_st = st.to_c()
@@ -298,25 +381,9 @@ def main_dsp(a):
         cpu = {"value": n * S * F / cdt, "unit": "stereo frames/s", "cores": 1, "kind": "port",
                "sample": f"{n} ticks x {S} sources x {F} frames ({cdt:.1f} s) through or_dsp_process "
                          f"(oracle/art_oracle.c, gcc -O3 -ffp-contract=off), one thread"}
-    value = frames_all / dt
-    res = {
-        "metric": "spatializer DSP stereo frames/s (per-sample OnAudioFilterRead chain)",
-        "value": value,
-        "unit": "stereo frames/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": dt / a.steps * 1e3,
-        "realtime_sources_at_48k": value / sr,
+    res.update({
         "p50_host_tick_ms": statistics.median(host_ms),
         "p50_host_tick_ms_note": "art_dsp_process on host buffers: pack, H2D, kernel, D2H, unpack (PCIe-inclusive)",
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": f"dsp tick: {S} spatializers (config{cfg.index} sources) x {F} stereo frames @ 48 kHz",
-                   "sources_per_gpu": S, "frames": F, "grouped_by_filter_class": bool(a.dsp_sort), "parallelism": f"source-sharded x{world} (replicas, no collective)"},
         "roofline": {"bound": "hbm", "achieved": big_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": big_gbs / HBM_PEAK_GBS, "traffic": traffic, "kernel": "dsp_tiled_kernel",
                      "kernel_ms": big_ms, "batch_sources": B, "algorithmic_bytes": big_bytes,
@@ -326,7 +393,7 @@ def main_dsp(a):
                      "tick": {"kernel_ms": kern_ms, "achieved": tick_gbs, "frac": tick_gbs / HBM_PEAK_GBS,
                               "algorithmic_bytes": tick_bytes}},
         "cpu_baseline": cpu,
-    }
+    })
     print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()
@@ -353,8 +420,10 @@ def main_dirs(a):
     dt = time.perf_counter() - t0
     k_ms = e0.elapsed_time(e1) / a.steps
     gbs = n * 6 / (k_ms * 1e-3) / 1e9  # 6 B (half3) written per direction, nothing read
+    if a.dump_outputs:  # half3 directions as the float32 values they encode
+        write_outputs(a.dump_outputs, {"directions": d.cpu().numpy().view(np.float16).reshape(n, 3).astype(np.float32)})
     cpu = None
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         m = min(n, 1 << 20)
         host = np.zeros((m, 3), np.uint16)
         reps, t1 = 0, time.perf_counter()
@@ -374,7 +443,7 @@ def main_dirs(a):
         "roofline": {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
                      "traffic": None, "kernel": "fibonacci_kernel", "kernel_ms": k_ms,
                      "note": "6 B written per direction; double-precision cos/sin make it FP64-VALU-heavy"},
-        "cpu_baseline": cpu}))
+        "full": bool(a.full), "cpu_baseline": cpu}))
 
 
 def lib_sha256():
@@ -518,7 +587,8 @@ def main_cpu(a):
     scene, org, params = art.synth(cfg, C_scale=a.collider_scale)
     host = host_cpu_info()
     res = {}
-    for label, threads in (("n", host["threads_used"]), ("one", 1)):
+    legs = (("n", host["threads_used"]), ("one", 1)) if a.full else (("n", host["threads_used"]),)  # one thread: --full
+    for label, threads in legs:
         os.environ["ART_CPU_THREADS"] = str(threads)
         with art.Context(0) as ctx:
             out = art.FanOutputs(cfg.S, cfg.R, cfg.H, cfg.T, 1, hits=True, dsp=params.dsp is not None)
@@ -528,6 +598,8 @@ def main_cpu(a):
             tests = sum(ctx.last_test_counts().values())
             ctx.set_flags(0)
             p50, mean, n = cpu_frames(ctx, frame, a.cpu_seconds / 2)
+        if label == "n" and a.dump_outputs:
+            write_outputs(a.dump_outputs, fan_output_arrays(out))
         res[label] = {"threads": threads, "p50_frame_ms": p50, "mean_frame_ms": mean, "frames": n,
                       "tests_per_frame": tests, "tests_per_s": tests / (mean * 1e-3)}
     os.environ.pop("ART_CPU_THREADS", None)
@@ -538,7 +610,7 @@ def main_cpu(a):
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"config{cfg.index}: {cfg.description}", "backend": "art_create(device_mask = 0)",
                    "fans": cfg.S, "rays": cfg.R, "colliders": cfg.C, "targets": cfg.T, "max_hits_per_ray": cfg.H},
-        "threads_n": res["n"], "threads_1": res["one"], "host": host}))
+        "full": bool(a.full), "threads_n": res["n"], "threads_1": res.get("one"), "host": host}))
 
 
 def verify_allgather(ctx, dist, backend, world, rank, org_all, S_total, d_org, S, d_blk, stride, dev, sp, timed_full=None):
@@ -679,7 +751,7 @@ def main():
             return
         ctx.launch_device(d_org.data_ptr(), S, d_blk.data_ptr(), 0, sp)
         if dist_on:
-            art.dist.all_gather_fan_blocks(d_blk[: S * stride], S_total, stride, world)
+            mode["gathered"] = art.dist.all_gather_fan_blocks(d_blk[: S * stride], S_total, stride, world)
 
     def drain():  # the pending all-gathers (their output is then ready on the launch stream)
         if og is not None:
@@ -754,6 +826,51 @@ def main():
         verify["overlapped_allgather"] = overlap
         if overlap_tune is not None:
             verify["overlap_tune"] = overlap_tune
+    if dist_on:
+        dt = float(allreduce(dt, torch.float64, dist.ReduceOp.MAX))
+        tests_all = float(allreduce(tests_rank, torch.float64))
+    else:
+        tests_all = float(tests_rank)
+    if a.dump_outputs and rank == 0:
+        # what the last timed step left for its caller: every fan's result block (N > 1: the all-gathered blocks)
+        blocks = (last_full if last_full is not None else mode["gathered"]) if dist_on else d_blk
+        write_outputs(a.dump_outputs, fan_block_arrays(blocks, lay, S_total if dist_on else S, cfg, params.dsp is not None))
+
+    value = tests_all * steps / dt
+    res = {
+        "metric": "ray-collider tests/sec + p50 per-frame batch ms, 256src\u00d7512ray\u00d74096col",  # BASELINE.json "metric"
+        "value": value,
+        "unit": "equivalent ray-collider tests/s",
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": a.warmup,
+        "prewarm": {"seconds": a.prewarm_s, "frames": prewarm_frames,
+                    "note": "untimed frames before the warmup steps (GPU clock ramp of a fresh process); the timed "
+                            "region holds exactly `steps` frames"},
+        "ms_per_step": dt / steps * 1e3,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"config{cfg.index}: {cfg.description}", "fans_total": S_total, "fans_rank0": S,
+                   "rays": cfg.R, "colliders": cfg.C, "targets": cfg.T, "max_hits_per_ray": cfg.H,
+                   "reference_tests_per_frame_rank0": tests_rank, "reference_tests_per_frame_all": tests_all,
+                   "parallelism": f"fan-sharded x{world}" + (f" + all-gather ({'RCCL' if a.dist_backend == 'nccl' else 'gloo'})"
+                                                              if dist_on else "")},
+        "allgather_verified": verify["verified"] if verify else None,
+        "allgather_verify": verify,
+        "allgather_bytes": (S_total * lay["stride"]) if dist_on else None,
+        "lib_sha256": lib_sha256(),
+        "full": bool(a.full),
+    }
+    if not a.full:  # a plain run: the timed steps and their figure only
+        ctx.close()
+        if rank == 0:
+            print(json.dumps(res))
+        if dist_on:
+            dist.destroy_process_group()
+        return
 
     # Kernel durations: untimed passes of the same launches after the timed region, HIP events on
     # the streams the kernels run on. Pass 1: the frame's stages only (raytrace stage, permeation
@@ -793,11 +910,6 @@ def main():
     torch.cuda.synchronize()
     executed = ctx.executed_counts()
     ctx.set_flags(0)
-    if dist_on:
-        dt = float(allreduce(dt, torch.float64, dist.ReduceOp.MAX))
-        tests_all = float(allreduce(tests_rank, torch.float64))
-    else:
-        tests_all = float(tests_rank)
 
     # p50 per-frame latency through the Unity-facing API (host arrays, H2D + kernels + D2H)
     frame_ms = []
@@ -871,35 +983,11 @@ def main():
     if world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(cfg, scene, params, org, a.cpu_seconds)
 
-    value = tests_all * steps / dt
-    res = {
-        "metric": "ray-collider tests/sec + p50 per-frame batch ms, 256src\u00d7512ray\u00d74096col",  # BASELINE.json "metric"
-        "value": value,
-        "unit": "equivalent ray-collider tests/s",
-        "n_gpus": world,
-        "steps": steps,
-        "warmup": a.warmup,
-        "prewarm": {"seconds": a.prewarm_s, "frames": prewarm_frames,
-                    "note": "untimed frames before the warmup steps (GPU clock ramp of a fresh process); the timed "
-                            "region holds exactly `steps` frames"},
-        "ms_per_step": dt / steps * 1e3,
+    res.update({
         "p50_frame_ms": statistics.median(frame_ms) if frame_ms else None,
         "p50_frame_ms_note": "art_schedule..art_complete on rank 0, host arrays, H2D + kernels + D2H (PCIe-inclusive)",
         "dynamic": dyn,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": f"config{cfg.index}: {cfg.description}", "fans_total": S_total, "fans_rank0": S,
-                   "rays": cfg.R, "colliders": cfg.C, "targets": cfg.T, "max_hits_per_ray": cfg.H,
-                   "reference_tests_per_frame_rank0": tests_rank, "reference_tests_per_frame_all": tests_all,
-                   "parallelism": f"fan-sharded x{world}" + (f" + all-gather ({'RCCL' if a.dist_backend == 'nccl' else 'gloo'})"
-                                                              if dist_on else "")},
         "allgather_ms": allgather_ms,
-        "allgather_verified": verify["verified"] if verify else None,
-        "allgather_verify": verify,
-        "allgather_bytes": (S_total * lay["stride"]) if dist_on else None,
         "allgather_note": (f"HIP events on the launch stream around the all-gather of {n_pass} untimed frames after the "
                            "timed region, max over ranks; " + ("in the timed steps each frame's all-gather runs beside the "
                            "next frame's kernels (RCCL stream, two result blocks alternating); every gather is inside "
@@ -953,9 +1041,8 @@ def main():
                       "frames_timed": n_rt, "kernel_marks_dropped": keach["kernel_marks_dropped"],
                       "note": f"pass 1 (stage events only, {n_pass} untimed frames after the timed "
                                                     "region); per kernel family: pass 2 (ART_CTX_TIME_EACH_KERNEL)"},
-        "lib_sha256": lib_sha256(),
         "cpu_baseline": cpu,
-    }
+    })
     print(json.dumps(res))
     if dist_on:
         dist.destroy_process_group()

@@ -172,7 +172,7 @@ def test_bench_two_ranks_gloo_strong_shards():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--config", "4", "--collider-scale", "0.0625", "--steps", "3", "--warmup", "1", "--frames", "1",
+    common = ["--full", "--config", "4", "--collider-scale", "0.0625", "--steps", "3", "--warmup", "1", "--frames", "1",
               "--no-cpu-baseline", "--no-dynamic"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
 
@@ -214,7 +214,7 @@ def test_bench_rccl_branch_one_rank():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--force-dist",
-                        "--steps", "100", "--warmup", "2", "--frames", "1", "--no-cpu-baseline", "--no-dynamic"],
+                        "--full", "--steps", "100", "--warmup", "2", "--frames", "1", "--no-cpu-baseline", "--no-dynamic"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-4000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -7,7 +7,7 @@ for rep in $(seq 1 ${AB_REPS:-1}); do
   for c in ${AB_CONFIGS:-2}; do
     for v in "$@"; do
       log=gpurun_out/ab/${v}_c$c.log
-      ART_LIB=$PWD/variants/libart_$v.so timeout -k 10 240 python bench.py --config $c --no-cpu-baseline --no-dynamic --frames 3 > $log 2>&1
+      ART_LIB=$PWD/variants/libart_$v.so timeout -k 10 240 python bench.py --full --config $c --no-cpu-baseline --no-dynamic --frames 3 > $log 2>&1
       python3 -c "
 import json; d=json.loads([l for l in open('$log').read().splitlines() if l.startswith('{')][-1])
 k={n: round(x * 1e3, 1) for n, x in d['kernel_ms'].items() if isinstance(x, float) and n not in ('raytrace', 'permeate', 'reduce')}

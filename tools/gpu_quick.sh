@@ -11,7 +11,7 @@ if [ "${3:-}" = "tests" ]; then
   timeout -k 10 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread > "$out/pytest_gpu.log" 2>&1 || { tail -40 "$out/pytest_gpu.log"; exit 1; }
   tail -1 "$out/pytest_gpu.log"
 fi
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py --config $cfg --no-cpu-baseline --no-dynamic --frames 5 --steps 50 > "$out/trace.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py --full --config $cfg --no-cpu-baseline --no-dynamic --frames 5 --steps 50 > "$out/trace.log" 2>&1
 python3 tools/kstats.py "$out/trace/run_kernel_stats.csv"
-timeout -k 10 300 python bench.py --config $cfg --no-cpu-baseline --no-dynamic > "$out/bench.log" 2>&1
+timeout -k 10 300 python bench.py --full --config $cfg --no-cpu-baseline --no-dynamic > "$out/bench.log" 2>&1
 tail -1 "$out/bench.log" | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); print('value', r['value'], 'ms_per_step', r['ms_per_step'], 'rt_ms', r['kernel_ms'], 'frac', r['roofline']['frac'])"

@@ -16,7 +16,7 @@ if [ "${3:-}" = "tests" ]; then
 fi
 short="--config $cfg --no-cpu-baseline --no-dynamic"
 echo "[gpu_round] kernel trace"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py $short --frames 5 --steps 50 > "$out/trace.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py --full $short --frames 5 --steps 50 > "$out/trace.log" 2>&1
 for c in FETCH_SIZE WRITE_SIZE "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU"; do
   n=$(echo "$c" | cut -d' ' -f1)
   echo "[gpu_round] pmc $c"
@@ -27,7 +27,7 @@ done
 python3 tools/prof_summary.py "$out" "$tag" "$cfg" > "$out/prof_summary.log" 2>&1
 cp "profiles/traffic_config$cfg.json" "$out/"
 echo "[gpu_round] bench"
-timeout -k 10 400 python bench.py --config $cfg > "$out/bench.log" 2>&1
+timeout -k 10 400 python bench.py --full --config $cfg > "$out/bench.log" 2>&1
 tail -1 "$out/bench.log" > "$out/bench.json"
 cat "$out/bench.json"
 echo "[gpu_round] done"
