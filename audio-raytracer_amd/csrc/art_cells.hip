@@ -473,12 +473,6 @@ __global__ __launch_bounds__(256) void cells_start_kernel(CellBufs cb) {
   cb.start[i] = base + inc - v;
 }
 
-size_t cells_scan_temp_bytes(int T, uint32_t cap) {  // (no library scratch since round 5: cells_block_scan_kernel)
-  (void)T;
-  (void)cap;
-  return 0;
-}
-
 // Entry capacity: 128 cells per (target, collider) on average (a collider near its target spans
 // hundreds, a far one a few); a target whose lists do not fit falls back to testing every collider.
 size_t cells_entry_cap(int T, int C) {

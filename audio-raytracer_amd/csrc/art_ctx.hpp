@@ -1,0 +1,289 @@
+// art_ctx.hpp — the context behind the C ABI (internal to libart.so): per-device and per-context
+// state grouped by owner, and the functions that cross the host units art_capi.cpp, art_frame.cpp,
+// art_scene.cpp, art_enqueue.cpp, art_store.cpp and art_dsp_api.cpp.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstddef>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/art_colliders.h"
+#include "../../include/art_device.h"
+#include "art_cpu.hpp"
+#include "art_internal.hpp"
+
+struct art_ctx;
+
+namespace art {
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// per collider kind (sphere, AABB, OBB): record size and offset of its audio_target_id
+constexpr size_t kRecSize[3] = {sizeof(art_sphere), sizeof(art_aabb), sizeof(art_obb)};
+constexpr size_t kTidOff[3] = {offsetof(art_sphere, audio_target_id), offsetof(art_aabb, audio_target_id),
+                               offsetof(art_obb, audio_target_id)};
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool reserve(size_t n) {
+    if (n <= cap) return true;
+    release();
+    if (hipMalloc(&p, std::max<size_t>(n, 256)) != hipSuccess) { p = nullptr; return false; }
+    cap = std::max<size_t>(n, 256);
+    return true;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+struct HostBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool reserve(size_t n) {
+    if (n <= cap) return true;
+    release();
+    if (hipHostMalloc(&p, std::max<size_t>(n, 256), hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
+    cap = std::max<size_t>(n, 256);
+    return true;
+  }
+  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
+// Hands out the 256-B aligned sections of one device allocation in order (base 0: only their sizes).
+struct Carver {
+  uintptr_t base;
+  size_t off = 0;
+  template <class T>
+  T* take(size_t bytes) {
+    T* p = reinterpret_cast<T*>(base + off);
+    off = align_up(off + bytes, 256);
+    return p;
+  }
+};
+
+// Scalars of one frame that the kernels need, plus the derived batch tables.
+struct Frame {
+  int R = 0, H = 0, T = 0, TC = 0, bs = 0, nb = 0;
+  int ns = 0, na = 0, no = 0;
+  uint32_t stages = 0;
+  bool resident = false;               // colliders come from the resident store (art_colliders.h)
+  FrameParams fp{};
+  FanLayout L{};
+  std::vector<int2> slot_batch;        // permeation: [TC] ray range of the last batch writing slot s
+  std::vector<uint8_t> muffle_reset;   // raytrace: [TC] 1 if some batch resets slot s
+  std::vector<int> ray_order;          // lane slot -> ray index (direction-coherent at TC == 1)
+  std::vector<uint8_t> order_dirs;     // the half3 directions ray_order was computed from
+  // input staging layout (bytes)
+  size_t off_sph = 0, off_aabb = 0, off_obb = 0, off_tgt = 0, off_dirs = 0, off_vol = 0, off_muf = 0, off_tab = 0,
+         off_reset = 0, off_order = 0, raw_bytes = 0;
+  // bytes of the record allocation (carve_decoded, carve_sort, carve_cells), entry capacity of the cell lists
+  size_t soa_bytes = 0;
+  uint32_t cells_cap = 0;
+};
+
+// One device's part of the resident collider store (art_colliders.h): AoS lists, decoded records +
+// bounds, sync upload.
+struct StoreDev {
+  DevBuf raw, soa, upd;
+  int cap[3] = {0, 0, 0};
+  DecodedColliders dec{};       // the store's decoded records, with the counts of the last sync
+  int n[3] = {0, 0, 0};
+  bool fresh = true;            // capacity (re)allocated: every record must be uploaded
+  hipEvent_t done = nullptr;    // recorded after the last sync's upload + decode (on stream)
+  hipStream_t stream = nullptr; // the stream the last sync ran on (dv.stream or a device-path launch stream)
+  hipEvent_t epoch[2] = {nullptr, nullptr};  // after the last sync of an epoch of the update ring
+  bool epoch_pending[2] = {false, false};
+};
+
+// An art_launch_device frame still running on the caller's stream reads the scene (records, sorted
+// copies, BVH) and uses the context's shared buffers (accumulators, pairs, side streams): work on
+// dv.stream that rewrites or reuses them waits for it first.
+// The completion event of those frames is recorded only when something has to wait for them: an
+// event record between frames costs the launch stream ~5 us of GPU idle per frame (kernel trace,
+// DESIGN.md §4), so back-to-back frames on one stream record none. The caller's stream of the last
+// frame must still exist at the next call that touches the scene (art.h, streams).
+// With ART_CTX_EVENT_EACH_LAUNCH the event is recorded by art_launch_device itself (recorded), so
+// the caller may destroy or recycle its stream right after the call.
+struct LaunchFence {
+  hipEvent_t done = nullptr;     // after the last art_launch_device frame (caller's stream)
+  bool pending = false;          // work on dv.stream waits for it before reusing the scene / buffers
+  hipStream_t stream = nullptr;  // the caller's stream of that frame
+  bool recorded = false;         // done already recorded after that frame
+  int mark_done(art_ctx* c);                // record done on the frame's stream (once per frame)
+  int wait(art_ctx* c, hipStream_t waiter); // a pending frame: waiter waits for it, nothing is pending then
+};
+
+// Host-API frames: the inputs of the last full upload (bytes, layout key, buffers) and the scene
+// built from them; a frame whose packed inputs are byte-identical skips the H2D copy, the record
+// decode and the BVH build (the Unity caller passes unchanged collider arrays every frame).
+struct UploadCache {
+  std::vector<uint8_t> raw;
+  int key[10] = {};
+  const void* raw_p = nullptr;
+  const void* soa_p = nullptr;
+  bool valid = false;
+  DevScene sc{};
+};
+
+// Resident scenes: the sorted copies / BVH in dv.soa were built for store generation gen (~0: none)
+// with these counts; later frames reuse them (refit when the store changed).
+struct SortedCache {
+  uint64_t gen = ~0ull;
+  const void* soa = nullptr;
+  int n[3] = {-1, -1, -1};
+  DevScene sc{};
+  bool matches(const Frame& f, const void* soa_p) const {
+    return f.resident && gen != ~0ull && soa == soa_p && n[0] == f.ns && n[1] == f.na && n[2] == f.no;
+  }
+};
+
+struct Device {
+  int id = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;
+  DevBuf raw, soa, origins, block, acc, counts;
+  DevBuf exec;  // executed-work counters (ART_CTX_COUNT_EXECUTED)
+  DevBuf cones; // the cell cone table (art_cells.hip), uploaded once
+  CellBufs cb{};  // muffle candidate list buffers of the current scene (upload_scene)
+  DevBuf pairs; // global visibility pairs of the split raytrace path
+  DevBuf dsp;   // per-sample DSP batch (art_dsp_process): samples, offsets, frames, params, states
+  StoreDev store;
+  LaunchFence fence;
+  uint64_t exec_launches = 0;
+  int fan_begin = 0, fan_count = 0;
+  size_t in_off = 0;  // art_schedule: this shard's [origins | permeation slots] in the input staging
+  DevScene sc{};
+  SortBufs sb{};  // buffers of the spatially sorted scene copy (art_bvh.hip), set by upload_scene
+  SortedCache sorted;
+  UploadCache last;
+  bool bound = false;
+  // side stream of the permeation job: it runs beside the raytrace stage (the reference schedules
+  // the two jobs independently, AudioRayTracer.cs:191,213), joined before the reduce job (:237);
+  // a rebuilt scene's cell lists build there beside the BVH
+  SideStream side;
+  SideStream echo;  // the echo visibility beside the muffle kernel
+  std::vector<hipEvent_t> ev_pool;  // timing events (start/stop pairs)
+  std::vector<std::pair<int, size_t>> ev_used;  // (EvKind, pool index of start)
+  int marks_dropped = 0;                          // per-kernel marks past the pairs (art_kernel_timing)
+};
+
+// The resident collider store of a context: the NextBatch mirror per kind, dirty marks, the last
+// sync's counts.
+struct ColliderStore {
+  struct Kind {
+    std::vector<uint8_t> recs;      // count * size bytes
+    int count = 0;
+    std::vector<uint8_t> dirty;     // per record
+    std::vector<int> dirty_list;
+  } kinds[3];
+  int synced[3] = {0, 0, 0};
+  bool store_synced = false;
+  // the synced records the resident scene's muffle cell lists were built from (cell_still_valid)
+  std::vector<uint8_t> cell_base[3];
+  bool cell_base_ok = false;
+  uint64_t sync_gen = 0;         // bumped by every art_colliders_sync that changed a record
+  // audio_target_id of every synced record and their histogram (index = id + 32768), kept
+  // incrementally from the dirty records (permeation loss test counts of counting frames)
+  std::vector<int16_t> synced_tid[3];
+  std::vector<int> tid_hist[3];
+  art_collider_sync_stats last_sync{};
+  std::vector<uint8_t> cpu_recs[3];  // CPU backend: the records at the last sync
+  // pinned update images of art_colliders_sync, a ring (sync s uses slot s % kUpdRing): a slot is
+  // reused only after the previous epoch's syncs are done (one event per epoch, not per sync)
+  static constexpr int kUpdRing = 8;
+  HostBuf h_upd[kUpdRing];
+  uint64_t upd_seq = 0;
+};
+
+}  // namespace art
+
+struct art_ctx {
+  std::vector<art::Device> devs;   // empty for the CPU backend
+  art::CpuEngine* cpu = nullptr;   // art_create(0): the CPU backend (art_cpu.cpp)
+  std::string err;
+  uint32_t flags = 0;
+  art::HostBuf h_in, h_block;
+  art::HostBuf h_dsp;            // staging of art_dsp_process
+  art::Frame fr;                 // frame of the bound scene / last schedule
+  // in-flight frame
+  bool inflight = false;
+  art_handle handle = 0;
+  uint64_t next_handle = 1;
+  std::vector<art_fan> fans;
+  bool counted = false;
+  art_test_counts last_counts{};
+  bool has_counts = false;
+  std::vector<uint64_t> nonowned;  // per type (s, a, o): sum over targets of non-owned colliders
+  art::ColliderStore store;
+  // Host phases of the Unity-facing frame (ART_HOST_TIMES=1 in the environment at art_create:
+  // steady_clock marks in art_schedule / art_complete, means printed by art_destroy to stderr).
+  struct HostPhases {
+    bool on = false;
+    uint64_t frames = 0;
+    double us[8] = {};
+  } hp;
+};
+
+namespace art {
+
+struct PhaseClock {
+  art_ctx::HostPhases* hp;
+  std::chrono::steady_clock::time_point t;
+  explicit PhaseClock(art_ctx::HostPhases* h) : hp(h && h->on ? h : nullptr) { if (hp) t = std::chrono::steady_clock::now(); }
+  void mark(int phase) {
+    if (!hp) return;
+    const auto n = std::chrono::steady_clock::now();
+    hp->us[phase] += std::chrono::duration<double, std::micro>(n - t).count();
+    t = n;
+  }
+};
+
+int fail(art_ctx* c, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+
+#define HIP_TRY(ctx, expr)                                                                          \
+  do {                                                                                              \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess) return art::fail(ctx, ART_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+// art_frame.cpp
+int validate_desc(art_ctx* c, const art_frame_desc* d);
+FanLayout make_layout(const art_frame_desc* d, uint32_t out_flags);
+void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts = nullptr);
+void pack_inputs(const art_frame_desc* d, const Frame& f, uint8_t* h);
+struct ConeTable {
+  CellCone cone[kCells];
+  float alpha_max = 0.0f;
+  ConeTable();
+};
+const ConeTable& cone_table();
+// The sections of a frame's record allocation, carved in this order: the decoded records (empty
+// when the store holds them), the sorted scene copy and BVH (art_bvh.hip), the muffle cell lists
+// (art_cells.hip; cones and compact are set by upload_scene).
+DecodedColliders carve_decoded(Carver& c, const Frame& f);
+SortBufs carve_sort(Carver& c, const Frame& f);
+CellBufs carve_cells(Carver& c, const Frame& f);
+
+// art_scene.cpp
+int ensure_side(art_ctx* c, SideStream& s);  // the stream and its fork / join events, created once
+int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in);
+void snapshot_cell_base(art_ctx* c);
+bool cell_still_valid(int kind, const uint8_t* now, const uint8_t* base);
+
+// art_enqueue.cpp
+// What an event pair of Device::ev_used times: a stage of the frame, or one kernel of the raytrace
+// stage (kEvKernel0 + MarkKind, ART_CTX_TIME_EACH_KERNEL).
+enum EvKind { kEvRaytrace = 0, kEvPermeate = 1, kEvReduce = 2, kEvKernel0 = 3 };
+hipEvent_t pool_event(Device& dv, size_t i);
+int enqueue_kernels(art_ctx* c, Device& dv, const Frame& f, const float* d_origins, int fan_count, uint8_t* d_block,
+                    hipStream_t st, bool count, const float* perm_in = nullptr, uint8_t* host_out = nullptr);
+int read_counts(art_ctx* c, Device& dv, hipStream_t st, art_test_counts* out, bool accumulate);
+bool compact_slots(const Frame& f, bool need_echo);
+int enqueue_device_frame(art_ctx* c, Device& dv, const Frame& f, const uint8_t* hin, uint8_t* hb, bool need_echo, bool count,
+                         bool inject_failure = false, PhaseClock* pc = nullptr);
+
+}  // namespace art

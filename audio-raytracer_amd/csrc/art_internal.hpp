@@ -99,6 +99,16 @@ struct DevScene {
   const uint32_t* cell_ok;        // [T]
   uint32_t cell_cap;
 };
+// The colliders as the caller gives them (AoS halves) and as the kernels read them (decoded hot and
+// cold records, bounds in global order: spheres, AABBs, OBBs).
+struct RawColliders { const art_sphere* sph; const art_aabb* aabb; const art_obb* obb; int ns, na, no; };
+struct DecodedColliders { SphereRec* sph; SphereCold* sphc; AabbRec* aabb; AabbCold* aabbc; ObbRec* obb; ObbCold* obbc; CullRec* cull; };
+inline void set_colliders(DevScene& sc, const DecodedColliders& d, const int n[3]) {
+  sc.sph = d.sph; sc.sphc = d.sphc; sc.ns = n[0];
+  sc.aabb = d.aabb; sc.aabbc = d.aabbc; sc.na = n[1];
+  sc.obb = d.obb; sc.obbc = d.obbc; sc.no = n[2];
+  sc.cull = d.cull;
+}
 // Motion slack of a listed collider (bounding radius r): the cell lists are built for its bounding
 // sphere grown by this much, so they stay valid while the collider keeps its extents and owner and
 // its centre stays within half of it of where the lists were built; art_colliders_sync then refits
@@ -112,7 +122,7 @@ struct DevScene {
 __host__ __device__ inline float cell_slack(float r) { return ART_CELL_SLACK_REL * r + ART_CELL_SLACK_ABS; }
 constexpr int kCellG = 32;                   // cells per cube-face axis
 constexpr int kCells = 6 * kCellG * kCellG;  // cells per target
-// Cell cone (host table, art_capi.cpp): unit axis and cos / sin of the half-angle plus slack.
+// Cell cone (host table, art_frame.cpp ConeTable): unit axis and cos / sin of the half-angle plus slack.
 struct alignas(16) CellCone {
   float ax, ay, az, cos_a;
   float sin_a, pad0, pad1, pad2;
@@ -188,11 +198,9 @@ struct CellBufs {
   uint32_t* ok;                   // [T]
   unsigned long long* tcount;     // [T] entries per target (cells_block_sum_kernel), for the capacity check
   uint32_t cap;                   // entry capacity; 0: no lists (cells_enabled false), every muffle ray tests every collider
-  void* temp; size_t temp_bytes;  // (unused since round 5: no library scan or sort)
   void* geo;                      // [T * C] per-(target, collider) geometry (cells_geo_bytes)
   CullRec* box;                   // [1] the union of the colliders' bounds (cells_box_kernel: the BVH root's box)
 };
-size_t cells_scan_temp_bytes(int T, uint32_t cap);
 size_t cells_geo_bytes(int T, int C);
 bool cells_enabled(int T, int C);
 size_t cells_entry_cap(int T, int C);
@@ -230,16 +238,11 @@ enum ExecSlot { kExecSphere = 0, kExecAabb = 1, kExecObb = 2, kExecCullBox = 3, 
 struct DevCounts { unsigned long long v[9]; };
 
 // --- launchers (art_kernels.hip) ---
-void launch_prep(const art_sphere* sph, int ns, const art_aabb* aabb, int na, const art_obb* obb, int no,
-                 SphereRec* osph, SphereCold* osphc, AabbRec* oaabb, AabbCold* oaabbc, ObbRec* oobb, ObbCold* oobbc,
-                 CullRec* cull, hipStream_t st);
+void launch_prep(const RawColliders& in, const DecodedColliders& out, hipStream_t st);
 void launch_fibonacci(int count, art_half3* out, hipStream_t st);
 void launch_half_range(uint32_t first, uint32_t count, uint16_t* out, hipStream_t st);
 void launch_recip_range(uint32_t first, uint32_t count, uint32_t* out, hipStream_t st);
-void launch_scatter_prep(const int* idx_s, const art_sphere* rec_s, int ds, const int* idx_a, const art_aabb* rec_a,
-                         int da, const int* idx_o, const art_obb* rec_o, int dob, art_sphere* sph, art_aabb* aabb,
-                         art_obb* obb, int ns, int na, SphereRec* osph, SphereCold* osphc, AabbRec* oaabb,
-                         AabbCold* oaabbc, ObbRec* oobb, ObbCold* oobbc, CullRec* cull, hipStream_t st);
+void launch_scatter_prep(const ScatterArgs& a, hipStream_t st);
 void launch_raytrace(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins,
                      uint8_t* block, uint32_t* muffle_acc, DevCounts* counts, hipStream_t st);
 // Bytes of the visibility pair buffer of launch_raytrace_fast for this frame (fp.S fans).

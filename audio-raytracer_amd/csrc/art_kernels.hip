@@ -525,13 +525,11 @@ __global__ __launch_bounds__(64) void reduce_kernel(DevScene sc, FrameParams fp,
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-void launch_prep(const art_sphere* sph, int ns, const art_aabb* aabb, int na, const art_obb* obb, int no,
-                 SphereRec* osph, SphereCold* osphc, AabbRec* oaabb, AabbCold* oaabbc, ObbRec* oobb, ObbCold* oobbc,
-                 CullRec* cull, hipStream_t st) {
-  int n = ns + na + no;
+void launch_prep(const RawColliders& in, const DecodedColliders& out, hipStream_t st) {
+  int n = in.ns + in.na + in.no;
   if (n == 0) return;
-  hipLaunchKernelGGL(prep_kernel, dim3((n + 255) / 256), dim3(256), 0, st, sph, ns, aabb, na, obb, no, osph, osphc, oaabb,
-                     oaabbc, oobb, oobbc, cull);
+  hipLaunchKernelGGL(prep_kernel, dim3((n + 255) / 256), dim3(256), 0, st, in.sph, in.ns, in.aabb, in.na, in.obb, in.no,
+                     out.sph, out.sphc, out.aabb, out.aabbc, out.obb, out.obbc, out.cull);
 }
 
 // FibonacciDirectionsJobParallel.Execute (Jobs/FibonacciDirectionsJobParallel.cs:15-35), one lane
@@ -587,14 +585,12 @@ void launch_fibonacci(int count, art_half3* out, hipStream_t st) {
   hipLaunchKernelGGL(fibonacci_kernel, dim3((count + 255) / 256), dim3(256), 0, st, count, out);
 }
 
-void launch_scatter_prep(const int* idx_s, const art_sphere* rec_s, int ds, const int* idx_a, const art_aabb* rec_a,
-                         int da, const int* idx_o, const art_obb* rec_o, int dob, art_sphere* sph, art_aabb* aabb,
-                         art_obb* obb, int ns, int na, SphereRec* osph, SphereCold* osphc, AabbRec* oaabb,
-                         AabbCold* oaabbc, ObbRec* oobb, ObbCold* oobbc, CullRec* cull, hipStream_t st) {
-  const int n = ds + da + dob;
+void launch_scatter_prep(const ScatterArgs& a, hipStream_t st) {
+  const int n = a.ds + a.da + a.dob;
   if (n <= 0) return;
-  hipLaunchKernelGGL(scatter_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, st, idx_s, rec_s, ds, idx_a, rec_a, da,
-                     idx_o, rec_o, dob, sph, aabb, obb, ns, na, osph, osphc, oaabb, oaabbc, oobb, oobbc, cull);
+  hipLaunchKernelGGL(scatter_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a.idx_s, a.rec_s, a.ds, a.idx_a, a.rec_a,
+                     a.da, a.idx_o, a.rec_o, a.dob, a.sph, a.aabb, a.obb, a.ns, a.na, a.osph, a.osphc, a.oaabb, a.oaabbc,
+                     a.oobb, a.oobbc, a.cull);
 }
 
 void launch_raytrace(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins, uint8_t* block,

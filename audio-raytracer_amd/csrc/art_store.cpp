@@ -1,0 +1,388 @@
+// art_store.cpp — the resident collider store (include/art_colliders.h): the host mirror of the
+// caller's collider lists with dirty marks, and art_colliders_sync, which uploads the changed
+// records to every device as a plan (plan_sync) and four steps (stage_image, sync_device per
+// device, commit_sync).
+#include "art_ctx.hpp"
+
+using namespace art;
+
+namespace {
+
+// The store's device layout for the capacities cap[3]: the AoS lists in one buffer, the decoded
+// records and bounds in another (base 0: only the sizes, in the carvers' offsets).
+struct StoreViews {
+  art_sphere* sph; art_aabb* aabb; art_obb* obb;
+  DecodedColliders dec;
+};
+StoreViews store_views(const int cap[3], Carver& raw, Carver& soa) {
+  StoreViews v;
+  v.sph = raw.take<art_sphere>((size_t)cap[0] * sizeof(art_sphere));
+  v.aabb = raw.take<art_aabb>((size_t)cap[1] * sizeof(art_aabb));
+  v.obb = raw.take<art_obb>((size_t)cap[2] * sizeof(art_obb));
+  v.dec.sph = soa.take<SphereRec>((size_t)cap[0] * sizeof(SphereRec));
+  v.dec.sphc = soa.take<SphereCold>((size_t)cap[0] * sizeof(SphereCold));
+  v.dec.aabb = soa.take<AabbRec>((size_t)cap[1] * sizeof(AabbRec));
+  v.dec.aabbc = soa.take<AabbCold>((size_t)cap[1] * sizeof(AabbCold));
+  v.dec.obb = soa.take<ObbRec>((size_t)cap[2] * sizeof(ObbRec));
+  v.dec.obbc = soa.take<ObbCold>((size_t)cap[2] * sizeof(ObbCold));
+  v.dec.cull = soa.take<CullRec>((size_t)(cap[0] + cap[1] + cap[2]) * sizeof(CullRec));
+  return v;
+}
+
+// What one art_colliders_sync does, decided on the host before any device is given work.
+struct SyncPlan {
+  int n[3];                   // the lists' counts
+  bool counts_changed;        // against the last sync (true for the first)
+  bool fresh;                 // some device's capacity was (re)allocated: every record is uploaded
+  std::vector<int> lists[3];  // dirty records of each kind (all of them when fresh), ascending
+  // update image: [idx_s][rec_s][idx_a][rec_a][idx_o][rec_o], 16-B aligned sections
+  size_t off_idx[3], off_rec[3], bytes;
+  int nd;                     // dirty records over the kinds
+  bool cells_ok;              // every changed collider stayed within the muffle cell lists' slack
+  int slot, ep;               // the image's slot in the pinned ring and the ring's epoch (0 / 1)
+};
+
+// No HIP call, but it does change host state: it grows the devices' capacities (x2) and marks them
+// fresh (sync_device then frees and reallocates their buffers), and it takes the sync's generation
+// and ring sequence numbers.
+SyncPlan plan_sync(art_ctx& c) {
+  ColliderStore& s = c.store;
+  SyncPlan p;
+  for (int k = 0; k < 3; ++k) p.n[k] = s.kinds[k].count;
+  p.counts_changed = !s.store_synced;
+  for (int k = 0; k < 3; ++k) p.counts_changed |= p.n[k] != s.synced[k];
+  p.fresh = false;
+  for (Device& dv : c.devs) {  // a list outgrew the device capacity: everything is uploaded again
+    StoreDev& d = dv.store;
+    if (p.n[0] > d.cap[0] || p.n[1] > d.cap[1] || p.n[2] > d.cap[2] || !d.raw.p) {
+      for (int k = 0; k < 3; ++k) d.cap[k] = std::max({p.n[k], 2 * d.cap[k], 64});
+      d.fresh = true;
+    }
+    p.fresh |= d.fresh;
+  }
+  p.bytes = 0;
+  for (int k = 0; k < 3; ++k) {
+    auto& K = s.kinds[k];
+    std::vector<int>& l = p.lists[k];
+    if (p.fresh) {
+      l.resize((size_t)p.n[k]);
+      for (int i = 0; i < p.n[k]; ++i) l[(size_t)i] = i;
+    } else {
+      for (int i : K.dirty_list)
+        if (i < p.n[k] && K.dirty[(size_t)i]) l.push_back(i);
+      std::sort(l.begin(), l.end());
+      l.erase(std::unique(l.begin(), l.end()), l.end());
+    }
+    p.off_idx[k] = p.bytes; p.bytes = align_up(p.bytes + l.size() * 4, 16);
+    p.off_rec[k] = p.bytes; p.bytes = align_up(p.bytes + l.size() * kRecSize[k], 16);
+  }
+  if (c.cpu) p.bytes = 0;  // the CPU backend keeps no device copy (commit_sync snapshots the lists)
+  p.nd = (int)(p.lists[0].size() + p.lists[1].size() + p.lists[2].size());
+  if (p.nd || p.counts_changed) ++s.sync_gen;  // resident frames refit / rebuild their sorted copies
+  // the muffle cell lists need a rebuild unless every changed collider stayed within their slack
+  p.cells_ok = s.cell_base_ok && !p.counts_changed && !p.fresh;
+  for (int k = 0; p.cells_ok && k < 3; ++k) {
+    const size_t rs = kRecSize[k];
+    if (s.cell_base[k].size() < (size_t)p.n[k] * rs) { p.cells_ok = false; break; }
+    for (int i : p.lists[k])
+      if (!cell_still_valid(k, s.kinds[k].recs.data() + (size_t)i * rs, s.cell_base[k].data() + (size_t)i * rs)) {
+        p.cells_ok = false;
+        break;
+      }
+  }
+  // The update image goes to ring slot seq % kUpdRing. A new epoch reuses the ring: every sync of the
+  // previous epoch has finished reading its slot once that epoch's event (recorded after its last
+  // sync, on that sync's stream) has completed. Each sync's stream is ordered after the earlier
+  // syncs' (a launch on a new stream waits on the old one, a context-stream sync on the launch
+  // stream), so that one event covers the whole epoch.
+  const uint64_t seq = s.upd_seq++;
+  p.slot = (int)(seq % ColliderStore::kUpdRing);
+  p.ep = (int)((seq / ColliderStore::kUpdRing) & 1u);
+  return p;
+}
+
+// The pinned update image of the plan, in its ring slot (a new epoch first waits for the last one).
+int stage_image(art_ctx* c, const SyncPlan& p) {
+  ColliderStore& s = c->store;
+  if (p.slot == 0)
+    for (Device& dv : c->devs)
+      if (dv.store.epoch_pending[p.ep ^ 1]) {
+        HIP_TRY(c, hipSetDevice(dv.id));
+        HIP_TRY(c, hipEventSynchronize(dv.store.epoch[p.ep ^ 1]));
+        dv.store.epoch_pending[p.ep ^ 1] = false;
+      }
+  if (!p.bytes) return ART_OK;
+  if (!s.h_upd[p.slot].reserve(p.bytes)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
+  uint8_t* h = static_cast<uint8_t*>(s.h_upd[p.slot].p);
+  for (int k = 0; k < 3; ++k) {
+    const size_t rs = kRecSize[k];
+    for (size_t j = 0; j < p.lists[k].size(); ++j) {
+      const int i = p.lists[k][j];
+      memcpy(h + p.off_idx[k] + j * 4, &i, 4);
+      memcpy(h + p.off_rec[k] + j * rs, s.kinds[k].recs.data() + (size_t)i * rs, rs);
+    }
+  }
+  return ART_OK;
+}
+
+// The plan's dirty records in the update image at `image` (a device copy, or the pinned image as
+// the device sees it), scattered into the store's lists and decoded records.
+ScatterArgs scatter_args(const SyncPlan& p, const void* image, const StoreViews& v) {
+  const uint8_t* u = static_cast<const uint8_t*>(image);
+  ScatterArgs a;
+  a.idx_s = reinterpret_cast<const int*>(u + p.off_idx[0]); a.rec_s = reinterpret_cast<const art_sphere*>(u + p.off_rec[0]);
+  a.idx_a = reinterpret_cast<const int*>(u + p.off_idx[1]); a.rec_a = reinterpret_cast<const art_aabb*>(u + p.off_rec[1]);
+  a.idx_o = reinterpret_cast<const int*>(u + p.off_idx[2]); a.rec_o = reinterpret_cast<const art_obb*>(u + p.off_rec[2]);
+  a.ds = (int)p.lists[0].size(); a.da = (int)p.lists[1].size(); a.dob = (int)p.lists[2].size();
+  a.sph = v.sph; a.aabb = v.aabb; a.obb = v.obb;
+  a.ns = p.n[0]; a.na = p.n[1];
+  const DecodedColliders& d = v.dec;
+  a.osph = d.sph; a.osphc = d.sphc; a.oaabb = d.aabb; a.oaabbc = d.aabbc; a.oobb = d.obb; a.oobbc = d.obbc; a.cull = d.cull;
+  return a;
+}
+
+// The event that frees the ring for the epoch after the next, recorded after the epoch's last sync
+// once the device may have been given work that reads the slot: by record() on the normal exits of
+// sync_device (a failure fails the sync, as before), by the destructor on its error exits.
+struct EpochMark {
+  StoreDev& s;
+  const SyncPlan& p;
+  hipStream_t ss;
+  bool done = false;
+  int record(art_ctx* c) {
+    done = true;
+    if (p.slot != ColliderStore::kUpdRing - 1) return ART_OK;
+    if (!s.epoch[p.ep]) HIP_TRY(c, hipEventCreateWithFlags(&s.epoch[p.ep], hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(s.epoch[p.ep], ss));
+    s.epoch_pending[p.ep] = true;
+    return ART_OK;
+  }
+  ~EpochMark() { if (!done) (void)record(nullptr); }  // (no context: the first error's text is kept)
+};
+
+// One device's share of a sync, async on the stream it picks: scatter + decode of the dirty records
+// (or the full decode after a count change), the bound resident scene's refit and, outside the
+// slack, its cell lists.
+int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt) {
+  StoreDev& s = dv.store;
+  HIP_TRY(c, hipSetDevice(dv.id));
+  if (s.fresh) { s.raw.release(); s.soa.release(); }  // grown capacity: new buffers, every record uploaded
+  Carver raw{0}, soa{0};
+  store_views(s.cap, raw, soa);
+  if (!s.raw.reserve(raw.off) || !s.soa.reserve(soa.off) || (p.bytes && !s.upd.reserve(p.bytes)))
+    return fail(c, ART_E_NOMEM, "device allocation failed");
+  raw = Carver{reinterpret_cast<uintptr_t>(s.raw.p)};
+  soa = Carver{reinterpret_cast<uintptr_t>(s.soa.p)};
+  const StoreViews v = store_views(s.cap, raw, soa);
+  void* h = c->store.h_upd[p.slot].p;
+  // Device-path frames still read the records / BVH being rewritten. The sync runs on the stream of
+  // the last such frame when its completion is not recorded yet (the stream is valid until this
+  // call, art_device.h): stream order puts it after that frame and before the next launch on the
+  // same stream, with no cross-stream events (each costs the queue ~5-10 us of idle). Otherwise
+  // it runs on the context stream, after the frame's completion event.
+  const hipStream_t ss = (dv.fence.pending && !dv.fence.recorded) ? dv.fence.stream : dv.stream;
+  if (ss == dv.stream)
+    if (int rc = dv.fence.wait(c, dv.stream)) return rc;
+  s.stream = ss;
+  EpochMark epoch{s, p, ss};
+  // moved colliders of a bound resident scene: one launch scatters the records from the pinned image
+  // and refits the BVH (launch_sync_refit), below
+  const bool refit_follows = p.nd && dv.bound && c->fr.resident && !p.counts_changed;
+  const bool fused = refit_follows && (long long)p.n[0] + p.n[1] + p.n[2] <= kSyncRefitMax && dv.sc.bvh_levels > 0 && dv.sb.bvh;
+  if (p.nd && !fused) {
+    HIP_TRY(c, hipMemcpyAsync(s.upd.p, h, p.bytes, hipMemcpyHostToDevice, ss));
+    launch_scatter_prep(scatter_args(p, s.upd.p, v), ss);
+    HIP_TRY(c, hipGetLastError());
+  }
+  // a count change moves the bounds of the later kinds (global order spheres, AABBs, OBBs)
+  if (p.counts_changed && !p.fresh && p.n[0] + p.n[1] + p.n[2] > 0) {
+    launch_prep(RawColliders{v.sph, v.aabb, v.obb, p.n[0], p.n[1], p.n[2]}, v.dec, ss);
+    HIP_TRY(c, hipGetLastError());
+  }
+  // stream-ordered: frames on ss follow. A sync on the context stream records done, which
+  // device-path launches on other streams wait on (a refit below records it after its kernels). A
+  // sync on the launch stream records nothing (each record costs the queue ~5 us): a launch on
+  // another stream waits on that stream's fence, work on dv.stream on it through LaunchFence::wait.
+  if (!s.done) HIP_TRY(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+  const bool lazy = ss != dv.stream;
+  if (!refit_follows && !lazy) HIP_TRY(c, hipEventRecord(s.done, ss));
+  s.dec = v.dec;
+  for (int k = 0; k < 3; ++k) s.n[k] = p.n[k];
+  s.fresh = false;
+  if (!(dv.bound && c->fr.resident)) return epoch.record(c);
+  if (p.counts_changed) {
+    dv.bound = false;  // the sorted copies are sized by count: bind again
+    return epoch.record(c);
+  }
+  set_colliders(dv.sc, v.dec, p.n);  // the bound device-resident scene sees the new snapshot
+  if (!p.nd) return epoch.record(c);
+  // moved colliders: refit the sorted copies and the BVH in place (device only, no H2D)
+  if (fused) {
+    void* hd = nullptr;  // the pinned image as the device sees it
+    HIP_TRY(c, hipHostGetDevicePointer(&hd, h, 0));
+    if (!launch_sync_refit(scatter_args(p, hd, v), dv.sc, dv.sb, ss))
+      return fail(c, ART_E_DEVICE, "collider sync refit not applicable");
+    HIP_TRY(c, hipGetLastError());
+  } else if (launch_refit_scene(dv.sc, dv.sb, ss) != 0) {
+    (void)hipEventRecord(s.done, ss);
+    return fail(c, ART_E_DEVICE, "collider refit failed");
+  }
+  if (!p.cells_ok) {
+    if (launch_build_cells(dv.sc, dv.cb, ss) != 0) return fail(c, ART_E_DEVICE, "muffle cell lists failed");
+    cells_rebuilt = true;
+  }
+  if (dv.sorted.gen != ~0ull) dv.sorted.gen = c->store.sync_gen;
+  if (!lazy) HIP_TRY(c, hipEventRecord(s.done, ss));  // device-path launches wait for the sort too
+  return epoch.record(c);
+}
+
+// The host bookkeeping of a sync that every device took: dirty marks, counts, the audio_target_id
+// histograms, the cell lists' base records, the CPU backend's snapshot and the statistics.
+void commit_sync(art_ctx* c, const SyncPlan& p, bool cells_rebuilt) {
+  ColliderStore& s = c->store;
+  const int* n = p.n;
+  if (c->fr.resident) { c->fr.ns = n[0]; c->fr.na = n[1]; c->fr.no = n[2]; }
+  for (int k = 0; k < 3; ++k) {
+    auto& K = s.kinds[k];
+    for (int i : K.dirty_list)  // O(changes), not O(colliders)
+      if ((size_t)i < K.dirty.size()) K.dirty[(size_t)i] = 0;
+    K.dirty_list.clear();
+    s.synced[k] = n[k];
+    // audio_target_id histogram of the synced records: removed tail, then the dirty records
+    auto& tids = s.synced_tid[k];
+    auto& hist = s.tid_hist[k];
+    if (hist.empty()) hist.assign(65536, 0);
+    for (size_t i = (size_t)n[k]; i < tids.size(); ++i) hist[(size_t)(tids[i] + 32768)]--;
+    const size_t old_n = tids.size();
+    tids.resize((size_t)n[k], 0);
+    const size_t rs = kRecSize[k], tid_off = kTidOff[k];
+    for (int i : p.lists[k]) {
+      int16_t v;
+      memcpy(&v, K.recs.data() + (size_t)i * rs + tid_off, 2);
+      if ((size_t)i < old_n) hist[(size_t)(tids[(size_t)i] + 32768)]--;
+      tids[(size_t)i] = v;
+      hist[(size_t)(v + 32768)]++;
+    }
+  }
+  if (cells_rebuilt) snapshot_cell_base(c);
+  else if (!p.cells_ok) s.cell_base_ok = false;  // the lists (rebuilt at the next bind) no longer hold these records
+  if (c->cpu)  // the CPU backend reads the synced snapshot (JobBatch) of each list
+    for (int k = 0; k < 3; ++k) s.cpu_recs[k].assign(s.kinds[k].recs.begin(), s.kinds[k].recs.begin() + (size_t)n[k] * kRecSize[k]);
+  s.store_synced = true;
+  s.last_sync.dirty_records = p.nd;
+  s.last_sync.full_prep = (p.counts_changed || p.fresh) ? 1 : 0;
+  s.last_sync.reallocated = p.fresh ? 1 : 0;
+  s.last_sync.cells_rebuilt = cells_rebuilt ? 1 : 0;
+  s.last_sync.bytes_uploaded = p.nd ? p.bytes : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+ART_API int art_collider_add(art_ctx* c, int32_t kind, const void* rec, int32_t* out_id) {
+  if (!c) return ART_E_INVALID;
+  if (kind < 0 || kind > 2 || !rec) return fail(c, ART_E_INVALID, "art_collider_add: bad kind or record");
+  auto& K = c->store.kinds[kind];
+  if (K.count >= (1 << 24)) return fail(c, ART_E_UNSUPPORTED, "more than 2^24 colliders of one kind");
+  const size_t rs = kRecSize[kind];
+  K.recs.resize((size_t)(K.count + 1) * rs);
+  memcpy(K.recs.data() + (size_t)K.count * rs, rec, rs);
+  K.dirty.push_back(1);
+  K.dirty_list.push_back(K.count);
+  if (out_id) *out_id = K.count;  // AudioColliderId = NextBatch.Length before the add
+  K.count++;
+  return ART_OK;
+}
+
+ART_API int art_collider_set(art_ctx* c, int32_t kind, int32_t id, const void* rec) {
+  if (!c) return ART_E_INVALID;
+  if (kind < 0 || kind > 2 || !rec) return fail(c, ART_E_INVALID, "art_collider_set: bad kind or record");
+  auto& K = c->store.kinds[kind];
+  if (id < 0 || id >= K.count) return fail(c, ART_E_INVALID, "art_collider_set: id %d out of range [0, %d)", id, K.count);
+  const size_t rs = kRecSize[kind];
+  memcpy(K.recs.data() + (size_t)id * rs, rec, rs);
+  if (!K.dirty[(size_t)id]) { K.dirty[(size_t)id] = 1; K.dirty_list.push_back(id); }
+  return ART_OK;
+}
+
+ART_API int art_collider_set_many(art_ctx* c, int32_t kind, const int32_t* ids, const void* recs, int32_t n) {
+  if (!c) return ART_E_INVALID;
+  if (kind < 0 || kind > 2 || n < 0 || (n > 0 && (!ids || !recs)))
+    return fail(c, ART_E_INVALID, "art_collider_set_many: bad arguments");
+  auto& K = c->store.kinds[kind];
+  for (int32_t j = 0; j < n; ++j)  // validate first: all or nothing
+    if (ids[j] < 0 || ids[j] >= K.count)
+      return fail(c, ART_E_INVALID, "art_collider_set_many: id %d out of range [0, %d)", ids[j], K.count);
+  const size_t rs = kRecSize[kind];
+  const uint8_t* r = static_cast<const uint8_t*>(recs);
+  for (int32_t j = 0; j < n; ++j) {
+    const int id = ids[j];
+    memcpy(K.recs.data() + (size_t)id * rs, r + (size_t)j * rs, rs);
+    if (!K.dirty[(size_t)id]) { K.dirty[(size_t)id] = 1; K.dirty_list.push_back(id); }
+  }
+  return ART_OK;
+}
+
+ART_API int art_collider_remove_swapback(art_ctx* c, int32_t kind, int32_t id) {
+  if (!c) return ART_E_INVALID;
+  if (kind < 0 || kind > 2) return fail(c, ART_E_INVALID, "art_collider_remove_swapback: bad kind");
+  auto& K = c->store.kinds[kind];
+  if (id < 0 || id >= K.count) return ART_OK;  // skipped, as AudioColliderManager.SwapRemove (:92-93)
+  const size_t rs = kRecSize[kind];
+  const int last = K.count - 1;
+  if (id != last) {
+    memcpy(K.recs.data() + (size_t)id * rs, K.recs.data() + (size_t)last * rs, rs);
+    if (!K.dirty[(size_t)id]) { K.dirty[(size_t)id] = 1; K.dirty_list.push_back(id); }
+  }
+  K.count = last;
+  K.recs.resize((size_t)last * rs);
+  K.dirty.resize((size_t)last);
+  return ART_OK;
+}
+
+ART_API int art_collider_get(art_ctx* c, int32_t kind, int32_t id, void* rec) {
+  if (!c) return ART_E_INVALID;
+  if (kind < 0 || kind > 2 || !rec) return fail(c, ART_E_INVALID, "art_collider_get: bad kind or record");
+  const auto& K = c->store.kinds[kind];
+  if (id < 0 || id >= K.count) return fail(c, ART_E_INVALID, "art_collider_get: id %d out of range [0, %d)", id, K.count);
+  memcpy(rec, K.recs.data() + (size_t)id * kRecSize[kind], kRecSize[kind]);
+  return ART_OK;
+}
+
+ART_API int art_collider_count(art_ctx* c, int32_t kind) {
+  if (!c) return ART_E_INVALID;
+  if (kind < 0 || kind > 2) return fail(c, ART_E_INVALID, "art_collider_count: bad kind");
+  return c->store.kinds[kind].count;
+}
+
+ART_API int art_colliders_clear(art_ctx* c) {
+  if (!c) return ART_E_INVALID;
+  for (auto& K : c->store.kinds) {
+    K.recs.clear(); K.dirty.clear(); K.dirty_list.clear(); K.count = 0;
+  }
+  return ART_OK;
+}
+
+ART_API int art_colliders_last_sync(art_ctx* c, art_collider_sync_stats* out) {
+  if (!c || !out) return ART_E_INVALID;
+  *out = c->store.last_sync;
+  return ART_OK;
+}
+
+ART_API int art_colliders_sync(art_ctx* c) {
+  if (!c) return ART_E_INVALID;
+  if (c->inflight) return fail(c, ART_E_STATE, "art_colliders_sync: a frame is in flight (sync after art_complete)");
+  const auto& K = c->store.kinds;
+  if ((long long)K[0].count + K[1].count + K[2].count > kMaxColliders)
+    return fail(c, ART_E_UNSUPPORTED, "art_colliders_sync: more than %lld colliders", kMaxColliders);
+  const SyncPlan p = plan_sync(*c);
+  if (int rc = stage_image(c, p)) return rc;
+  bool cells_rebuilt = false;
+  for (Device& dv : c->devs)
+    if (int rc = sync_device(c, dv, p, cells_rebuilt)) return rc;
+  commit_sync(c, p, cells_rebuilt);
+  return ART_OK;
+}
+
+}  // extern "C"

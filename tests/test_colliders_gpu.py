@@ -341,7 +341,59 @@ def _jitter(recs, rng, scale):
     return out
 
 
-@pytest.mark.parametrize("ci", [2, 5])
+def test_sync_ring_wraps(fresh_ctx):
+    """21 syncs (the load, then 20 rounds of moves) go through the 8-slot ring of pinned update images
+    twice over: the syncs that start a new epoch wait for the one before the last. Moves, syncs and
+    device frames are issued back to back on one stream with no host wait; every frame's block must
+    equal a frame computed from its own collider snapshot."""
+    import torch
+    S, R = 8, 128
+    scene, org, params = art.synth(art.CONFIGS[2], S=S, R=R, C_scale=0.25)
+    store, model = ColliderStore(fresh_ctx), ListsModel()
+    load(store, model, scene)
+    store.sync()
+    model.synced()
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(5)
+    fr = art.Frame(scene, params, org, art.FanOutputs(S, R, params.max_hits_per_ray, scene.T, params.thread_count))
+    lay = art.fan_layout(fr)
+    fresh_ctx.set_flags(abi.ART_CTX_RESIDENT_COLLIDERS)
+    snapshots, blocks = [], []
+    try:
+        fresh_ctx.bind(resident_frame(fr))
+        d_org = torch.from_numpy(np.ascontiguousarray(org)).to(dev)
+        st = torch.cuda.current_stream().cuda_stream
+        for _ in range(20):
+            for k in KINDS:  # move a tenth of each kind far (the refit changes many bounds)
+                arr = model.array(k)
+                if not arr.size:
+                    continue
+                ids = rng.choice(arr.size, max(1, arr.size // 10), replace=False)
+                recs = _jitter(arr[ids], rng, 8.0)
+                store.set_many(k, ids.astype(np.int32), recs)
+                for j, i in enumerate(ids):
+                    model.set(k, int(i), recs[j])
+            store.sync()
+            model.synced()
+            snapshots.append(scene_with(scene, model))
+            blk = torch.zeros(S * lay["stride"], dtype=torch.uint8, device=dev)
+            fresh_ctx.launch_device(d_org.data_ptr(), S, blk.data_ptr(), 0, st)
+            blocks.append(blk)
+        torch.cuda.synchronize()
+    finally:
+        fresh_ctx.set_flags(0)
+    ref_ctx = art.Context(1)
+    try:
+        for rnd, (snap, blk) in enumerate(zip(snapshots, blocks)):
+            out = art.FanOutputs(S, R, params.max_hits_per_ray, scene.T, params.thread_count)
+            ref_ctx.run(art.Frame(snap, params, org, out))
+            got = art.unpack_block(blk.cpu().numpy(), lay, S, R, params.max_hits_per_ray, scene.T, 1)
+            assert all(got.equal(out).values()), (rnd, got.equal(out))
+    finally:
+        ref_ctx.close()
+
+
+@pytest.mark.parametrize("ci", [2, 3, 5])
 def test_small_moves_keep_cell_lists(fresh_ctx, ci):
     """Syncs whose moved colliders stay within the cell lists' motion slack (cell_slack) refit the
     BVH but keep the muffle cell lists; larger moves and size changes rebuild them. Every round's

@@ -11,13 +11,15 @@ mkdir -p "$root/variants"
 flags=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden "$@")
 # the shipped build's scheduler (audio-raytracer_amd/Makefile SCHED; ART_SCHED= for the default one)
 sched=(${ART_SCHED--mllvm -amdgpu-sched-strategy=max-ilp})
-for f in art_kernels art_trace art_cells art_dsp; do
-  hipcc "${flags[@]}" "${sched[@]}" -c "$pkg/csrc/$f.hip" -o "$tmp/$f.o" &
+# every source of the directory, as the Makefile lists them; art_bvh.hip keeps the default scheduler
+for f in "$pkg"/csrc/*.hip; do
+  b=$(basename "$f" .hip)
+  if [ "$b" = art_bvh ]; then hipcc "${flags[@]}" -c "$f" -o "$tmp/$b.o" &
+  else hipcc "${flags[@]}" "${sched[@]}" -c "$f" -o "$tmp/$b.o" & fi
 done
-hipcc "${flags[@]}" -c "$pkg/csrc/art_bvh.hip" -o "$tmp/art_bvh.o" &
-hipcc "${flags[@]}" "${sched[@]}" -x hip -c "$pkg/csrc/art_capi.cpp" -o "$tmp/art_capi.o" &
-hipcc "${flags[@]}" "${sched[@]}" -x hip -c "$pkg/csrc/art_synth.cpp" -o "$tmp/art_synth.o" &
-hipcc "${flags[@]}" "${sched[@]}" -x hip -c "$pkg/csrc/art_cpu.cpp" -o "$tmp/art_cpu.o" &
+for f in "$pkg"/csrc/*.cpp; do
+  hipcc "${flags[@]}" "${sched[@]}" -x hip -c "$f" -o "$tmp/$(basename "$f" .cpp).o" &
+done
 wait
 hipcc --offload-arch=gfx950 -shared -fPIC -rdynamic -o "$root/variants/libart_$name.so" "$tmp"/*.o
 rm -rf "$tmp"
