@@ -52,6 +52,18 @@ ART_CTX_COUNT_EXECUTED = 0x10
 ART_CTX_RESIDENT_COLLIDERS = 0x20  # art_colliders.h
 ART_CTX_TIME_EACH_KERNEL = 0x200
 ART_CTX_EVENT_EACH_LAUNCH = 0x400  # art_launch_device records its completion event (the caller may drop its stream)
+# art_debug_last_plan: the launch plan of the throughput raytrace stage (art_device.h)
+ART_PLAN_FUSED, ART_PLAN_HM, ART_PLAN_SPLIT, ART_PLAN_FOLD, ART_PLAN_PER_BOUNCE = 0x1, 0x2, 0x4, 0x8, 0x10
+ART_PLAN_TAB, ART_PLAN_OBB, ART_PLAN_EX, ART_PLAN_CHUNKED = 0x20, 0x40, 0x80, 0x100
+PLAN_NAMES = {ART_PLAN_FUSED: "FUSED", ART_PLAN_HM: "HM", ART_PLAN_SPLIT: "SPLIT", ART_PLAN_FOLD: "FOLD",
+              ART_PLAN_PER_BOUNCE: "PER_BOUNCE", ART_PLAN_TAB: "TAB", ART_PLAN_OBB: "OBB", ART_PLAN_EX: "EX",
+              ART_PLAN_CHUNKED: "CHUNKED"}
+
+
+def plan_names(bits: int) -> str:
+    return "|".join(n for b, n in PLAN_NAMES.items() if bits & b) or "0"
+
+
 ART_KIND_SPHERE, ART_KIND_AABB, ART_KIND_OBB = 0, 1, 2
 ART_OUT_HIT_RESULTS = 0x1
 # art_fan.ray_hit_ids: ColliderType (Enums/ColliderType.cs) << 30 | index in that type's array
@@ -207,6 +219,7 @@ SIGNATURES = {
     "art_kernel_timing": (I32, [VP, C.POINTER(art_kernel_times)]),
     "art_executed_counts": (I32, [VP, C.POINTER(art_exec_counts)]),
     "art_debug_leaf_order": (I32, [VP, C.POINTER(U32), I32]),
+    "art_debug_last_plan": (I32, [VP, C.POINTER(U32)]),
     # art_dsp.h
     "art_dsp_process": (I32, [VP, C.POINTER(art_spatializer_settings), C.POINTER(art_audio_source), I32, I32]),
     "art_dsp_source_params_get": (I32, [C.POINTER(art_spatializer_settings), C.POINTER(art_audio_source), I32,

@@ -273,6 +273,15 @@ class Context:
             self._raise(rc)
         return buf[:rc].copy()
 
+    def debug_last_plan(self) -> int:
+        """ART_PLAN_* bits of the launch plan the throughput raytrace stage took for the last frame
+        (art_debug_last_plan; diagnostics). 0 after a reference-order or counting frame."""
+        bits = C.c_uint32()
+        rc = self.lib.art_debug_last_plan(self.ptr, C.byref(bits))
+        if rc:
+            self._raise(rc)
+        return int(bits.value)
+
     def launch_device(self, d_origins: int, fan_count: int, d_block: int, out_flags: int = 0, stream: int | None = None):
         rc = self.lib.art_launch_device(self.ptr, d_origins, fan_count, d_block, out_flags, stream)
         if rc:

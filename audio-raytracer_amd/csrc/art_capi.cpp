@@ -43,7 +43,8 @@ namespace {
 // art_debug_leaf_order, ART_CTX_GRAPH removed — a growth 2.3 should have made a major bump; 3.0:
 // art_kernel_times per kernel family (kernel_ms / kernel_launches / kernel_marks_dropped, 80 B),
 // ART_CTX_TIME_EACH_KERNEL.
-constexpr uint32_t kAbiVersion = (3u << 16) | 1u;  // 3.1: ART_CTX_EVENT_EACH_LAUNCH, art_recip_exact_device
+// 3.1: ART_CTX_EVENT_EACH_LAUNCH, art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*
+constexpr uint32_t kAbiVersion = (3u << 16) | 2u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -619,6 +620,13 @@ ART_API int art_debug_leaf_order(art_ctx* c, uint32_t* out, int32_t cap) {
   HIP_TRY(c, hipDeviceSynchronize());
   if (m > 0) HIP_TRY(c, hipMemcpy(out, dv.sc.bvh_ref, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return m;
+}
+
+ART_API int art_debug_last_plan(art_ctx* c, uint32_t* bits) {
+  if (!c || !bits) return ART_E_INVALID;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
+  *bits = c->devs.empty() ? 0u : c->devs[0].last_plan;
+  return ART_OK;
 }
 
 ART_API int art_kernel_timing(art_ctx* c, art_kernel_times* out) {

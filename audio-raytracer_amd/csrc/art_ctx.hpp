@@ -154,6 +154,7 @@ struct Device {
   StoreDev store;
   LaunchFence fence;
   uint64_t exec_launches = 0;
+  uint32_t last_plan = 0;  // ART_PLAN_* bits of the last frame's throughput raytrace stage (art_debug_last_plan)
   int fan_begin = 0, fan_count = 0;
   size_t in_off = 0;  // art_schedule: this shard's [origins | permeation slots] in the input staging
   DevScene sc{};

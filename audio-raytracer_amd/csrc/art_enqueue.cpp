@@ -53,12 +53,13 @@ static void raytrace_fast(Device& dv, const Frame& f, const FrameParams& fp, con
     marks.ev = mev.data();
     marks.kind = mkind.data();
   }
+  dv.last_plan = fan_count > chunk ? ART_PLAN_CHUNKED : 0u;
   for (int b0 = 0; b0 < fan_count; b0 += chunk) {
     FrameParams fpc = fp;
     fpc.S = std::min(chunk, fan_count - b0);
-    launch_raytrace_fast(dv.sc, fpc, f.L, d_origins + 3 * (size_t)b0, d_block + (size_t)b0 * f.L.stride,
-                         acc + (size_t)b0 * (size_t)f.TC * f.T, order, dv.pairs.p, pair_count, st, dv.echo,
-                         marks.cap ? &marks : nullptr);
+    dv.last_plan |= launch_raytrace_fast(dv.sc, fpc, f.L, d_origins + 3 * (size_t)b0, d_block + (size_t)b0 * f.L.stride,
+                                         acc + (size_t)b0 * (size_t)f.TC * f.T, order, dv.pairs.p, pair_count, st, dv.echo,
+                                         marks.cap ? &marks : nullptr);
   }
   for (int k = 0; k < marks.used; ++k)  // pool index base + 2 k
     dv.ev_used.push_back({kEvKernel0 + mkind[(size_t)k], dv.ev_used.size() * 2});
@@ -78,6 +79,7 @@ int enqueue_kernels(art_ctx* c, Device& dv, const Frame& f, const float* d_origi
   const int2* slot_batch = reinterpret_cast<const int2*>(raw + f.off_tab);
   const uint8_t* muffle_reset = raw + f.off_reset;
   const bool fast = (f.stages & ART_STAGE_RAYTRACE) && !count && !(c->flags & ART_CTX_FORCE_REFERENCE_ORDER);
+  dv.last_plan = 0;  // (raytrace_fast sets it)
   const size_t acc_per_fan = (size_t)f.TC * f.T;
   // muffle accumulators, then (16-B aligned) the visibility pair counters: cleared by the first
   // nearest_first_kernel of each fast-path chunk, by one memset before the reference-order kernel

@@ -267,9 +267,10 @@ struct KernelMarks {
   int cap = 0, used = 0;
   int dropped = 0;           // launches that found no pair left (their family's time is then incomplete)
 };
-void launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins,
-                          uint8_t* block, uint32_t* muffle_acc, const int* ray_order, void* pair_buf,
-                          uint32_t* pair_count, hipStream_t st, const SideStream& echo, KernelMarks* marks = nullptr);
+// Returns the launch plan it took as ART_PLAN_* bits (art_device.h; 0 for an empty chunk).
+uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins,
+                              uint8_t* block, uint32_t* muffle_acc, const int* ray_order, void* pair_buf,
+                              uint32_t* pair_count, hipStream_t st, const SideStream& echo, KernelMarks* marks = nullptr);
 void launch_permeate(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins,
                      uint8_t* block, const int2* slot_batch, hipStream_t st);
 // (the collider sweep of every loss ray, art_kernels.hip: the reference-order and counting frames)

@@ -21,6 +21,7 @@
 #include <type_traits>
 #include <cstdlib>
 
+#include "../../include/art_device.h"
 #include "art_device_fns.hpp"
 #include "art_frame_math.hpp"
 
@@ -2000,10 +2001,10 @@ static void marked(KernelMarks* marks, int kind, hipStream_t s, F&& launch) {
   if (m) { (void)hipEventRecord(marks->ev[2 * marks->used + 1], s); marks->used++; }
 }
 
-void launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins,
-                          uint8_t* block, uint32_t* muffle_acc, const int* ray_order, void* pair_buf, uint32_t* pair_count,
-                          hipStream_t st, const SideStream& echo, KernelMarks* marks) {
-  if (fp.S == 0) return;
+uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins,
+                              uint8_t* block, uint32_t* muffle_acc, const int* ray_order, void* pair_buf, uint32_t* pair_count,
+                              hipStream_t st, const SideStream& echo, KernelMarks* marks) {
+  if (fp.S == 0) return 0;
   const unsigned groups = (unsigned)((size_t)fp.S * ((fp.R + 63) / 64));
   const bool obb = sc.no > 0;  // OBB-free scenes run instantiations without the OBB tests
   PairBufs pb = pair_bufs(pair_buf, fp);
@@ -2156,6 +2157,10 @@ void launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const FanLa
     (void)hipEventRecord(echo.join, echo.st);
     (void)hipStreamWaitEvent(st, echo.join, 0);
   }
+  // the plan taken (art_debug_last_plan): the branch of the chain above, then the switches on top
+  return (per_bounce ? (fold ? ART_PLAN_FOLD : ART_PLAN_PER_BOUNCE) : fused ? ART_PLAN_FUSED : hm ? ART_PLAN_HM
+          : split ? ART_PLAN_SPLIT : 0u) |
+         (tab ? ART_PLAN_TAB : 0u) | (obb ? ART_PLAN_OBB : 0u) | (fp.exec ? ART_PLAN_EX : 0u);
 }
 
 #ifdef ART_DIAG

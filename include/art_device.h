@@ -142,6 +142,24 @@ ART_API int art_kernel_timing(art_ctx* ctx, art_kernel_times* out);
  * written (the bound scene's collider count when cap allows) or a negative art error. Synchronizes. */
 ART_API int art_debug_leaf_order(art_ctx* ctx, uint32_t* out, int32_t cap);
 
+/* Diagnostics (tests, ABI 3.2): the launch plan the throughput raytrace stage chose for the most
+ * recent frame enqueued on the context's first device (art_schedule, art_launch_device), as
+ * ART_PLAN_* bits. Exactly one of FUSED / HM / SPLIT / FOLD / PER_BOUNCE is set per fan chunk; a
+ * frame that ran as several fan chunks also sets CHUNKED and ORs the chunks' bits. 0 when that
+ * frame ran no throughput stage (a reference-order or counting frame, a frame without
+ * ART_STAGE_RAYTRACE, no fans) or before any frame. The plan is decided on the host when the frame
+ * is enqueued: the call does not synchronize. */
+#define ART_PLAN_FUSED      0x001u /* one-hit, one batch slot, no hit outputs: nearest -> echo_muffle_kernel */
+#define ART_PLAN_HM         0x002u /* one-hit, one batch slot, hit outputs, small frame: echo rays from the nearest hits */
+#define ART_PLAN_SPLIT      0x004u /* the other one-hit frames: nearest -> path -> echo batches, muffle beside them */
+#define ART_PLAN_FOLD       0x008u /* multi-hit, one batch slot, no hit outputs: the path epilogue folded into nearest */
+#define ART_PLAN_PER_BOUNCE 0x010u /* the other multi-hit frames: per bounce nearest -> path + echo, one muffle */
+#define ART_PLAN_TAB        0x020u /* bounce 0 ran nearest_first_kernel<..., TAB> (shared-origin node table) */
+#define ART_PLAN_OBB        0x040u /* the instantiations with the OBB tests (the scene has OBBs) */
+#define ART_PLAN_EX         0x080u /* the ART_CTX_COUNT_EXECUTED counting instantiations */
+#define ART_PLAN_CHUNKED    0x100u /* more than one fan chunk */
+ART_API int art_debug_last_plan(art_ctx* ctx, uint32_t* bits);
+
 /* Context over an explicit list of HIP devices: fans of every art_schedule are sharded
  * contiguously over the list (one HIP stream, one scene copy and one set of buffers per entry).
  * An id may repeat: art_create_on({0, 0, 0}, 3, &ctx) runs the in-process multi-device split and

@@ -26,7 +26,7 @@ def declared_symbols():
 def test_headers_declare_expected_surface():
     names = declared_symbols()
     for n in ("art_create", "art_schedule", "art_is_completed", "art_complete", "art_destroy", "art_last_error",
-              "art_scene_bind", "art_launch_device", "art_synth_scene"):
+              "art_scene_bind", "art_launch_device", "art_synth_scene", "art_debug_leaf_order", "art_debug_last_plan"):
         assert n in names
 
 
@@ -78,8 +78,24 @@ def test_header_struct_sizes_match_bindings(tmp_path):
 def test_version():
     v = art.load_library().art_version()
     # 3.0: art_kernel_times per kernel family (a grown struct: major bump); 3.1: ART_CTX_EVENT_EACH_LAUNCH,
-    # art_recip_exact_device
-    assert v >> 16 == 3 and v & 0xffff >= 1
+    # art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*
+    assert v >> 16 == 3 and (v & 0xffff) >= 2
+
+
+def test_plan_bits_match_header():
+    """art_debug_last_plan (ABI 3.2): the binding's ART_PLAN_* values are the header's, distinct single
+    bits, and the CPU backend (no launch plans) refuses the query."""
+    hdr = open(os.path.join(ROOT, "include", "art_device.h")).read()
+    in_hdr = {m.group(1): int(m.group(2), 16) for m in re.finditer(r"#define (ART_PLAN_\w+)\s+(0x[0-9a-fA-F]+)u", hdr)}
+    assert set(in_hdr) == {"ART_PLAN_" + n for n in abi.PLAN_NAMES.values()}
+    for name, v in in_hdr.items():
+        assert getattr(abi, name) == v and v & (v - 1) == 0 and abi.PLAN_NAMES[v] == name[len("ART_PLAN_"):]
+    assert len(set(in_hdr.values())) == 9
+    assert abi.plan_names(abi.ART_PLAN_FOLD | abi.ART_PLAN_TAB) == "FOLD|TAB" and abi.plan_names(0) == "0"
+    with art.Context(0) as cpu:
+        bits = C.c_uint32(7)
+        assert cpu.lib.art_debug_last_plan(cpu.ptr, C.byref(bits)) == abi.ART_E_UNSUPPORTED
+        assert cpu.lib.art_debug_last_plan(cpu.ptr, None) == abi.ART_E_INVALID
 
 
 def test_no_gpu_fails_loudly():

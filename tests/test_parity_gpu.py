@@ -34,12 +34,33 @@ def _diff_report(a: art.FanOutputs, b: art.FanOutputs) -> str:
     return "\n".join(lines)
 
 
+def shipped_plan(scene, params):
+    """The launch plan launch_raytrace_fast (csrc/art_trace.hip) takes for a frame that asks for no hit
+    outputs, as art_debug_last_plan reports it (without ART_PLAN_TAB): one batch slot runs the plans
+    bench.py times and a host without hit outputs gets (FUSED at H = 1, FOLD above), several batch
+    slots the split or per-bounce plan; the OBB instantiations exactly when the scene has OBBs;
+    nothing when the raytrace stage is off."""
+    if not params.stages & abi.ART_STAGE_RAYTRACE:
+        return 0
+    one = params.max_hits_per_ray == 1
+    if params.thread_count == 1:
+        plan = abi.ART_PLAN_FUSED if one else abi.ART_PLAN_FOLD
+    else:
+        plan = abi.ART_PLAN_SPLIT if one else abi.ART_PLAN_PER_BOUNCE
+    return plan | (abi.ART_PLAN_OBB if scene.obbs.size else 0)
+
+
 def gpu_vs_oracle(ctx, scene, params, org, hits=False, stale=None, counts=True, prime=None):
-    """Run the frame through both raytrace implementations — the throughput stage (BVH nearest
-    hits, sorted-batch visibility; art_trace.hip) and the reference-order kernel (one ray per lane,
-    every collider in reference order; its counting variant gives the metric's test counts) — and
-    require each to equal the oracle bit for bit; the counting run's test counts must equal the
-    oracle's."""
+    """Run the frame four times and require each run to equal the oracle bit for bit:
+      1. the throughput stage (BVH nearest hits, sorted-batch visibility; art_trace.hip) with the
+         caller's `hits`. With hits=True that is the HM, split or per-bounce plan;
+      2. the reference-order kernel (one ray per lane, every collider in reference order);
+      3. its counting variant, whose test counts must equal the oracle's (counts=True);
+      4. the throughput stage again with no hit outputs and context flags 0, from the same stale
+         and primed contents: the plans the product ships (FUSED / echo_muffle_kernel at H = 1, FOLD
+         above, at one batch slot). The plan that ran is asserted (art_debug_last_plan), so a change
+         of the dispatch cannot quietly take these scenes off those kernels.
+    Returns the first run's outputs and the oracle's test counts."""
     S = org.shape[0]
     o_gpu = art.FanOutputs(S, scene.R, params.max_hits_per_ray, scene.T, params.thread_count, hits=hits,
                            dsp=params.dsp is not None)
@@ -50,6 +71,8 @@ def gpu_vs_oracle(ctx, scene, params, org, hits=False, stale=None, counts=True, 
     o_ref = o_gpu.copy()
     o_cnt = o_gpu.copy()
     o_ro = o_gpu.copy()
+    o_nh = o_gpu.copy()  # the same stale / primed slots, without the hit arrays
+    o_nh.hit_points = o_nh.hit_counts = o_nh.hit_ids = None
     cref = oracle.run_frame(art.Frame(scene, params, org, o_ref), threads=16)
     ctx.set_flags(0)
     ctx.run(art.Frame(scene, params, org, o_gpu))
@@ -58,15 +81,22 @@ def gpu_vs_oracle(ctx, scene, params, org, hits=False, stale=None, counts=True, 
     ctx.set_flags(abi.ART_CTX_FORCE_REFERENCE_ORDER)
     ctx.run(art.Frame(scene, params, org, o_ro))
     ctx.set_flags(0)
+    assert ctx.debug_last_plan() == 0  # no throughput stage ran
     eq = o_ro.equal(o_ref)
     assert all(eq.values()), f"reference-order kernel: {eq}\n{_diff_report(o_ro, o_ref)}"
     if counts:
         ctx.set_flags(abi.ART_CTX_COUNT_TESTS)
         ctx.run(art.Frame(scene, params, org, o_cnt))
         ctx.set_flags(0)
+        assert ctx.debug_last_plan() == 0
         eq = o_cnt.equal(o_ref)
         assert all(eq.values()), f"counting kernel: {eq}\n{_diff_report(o_cnt, o_ref)}"
         assert ctx.last_test_counts() == cref
+    ctx.run(art.Frame(scene, params, org, o_nh))
+    plan, want = ctx.debug_last_plan() & ~abi.ART_PLAN_TAB, shipped_plan(scene, params)
+    assert plan == want, f"no-hit-outputs leg ran {abi.plan_names(plan)}, expected {abi.plan_names(want)}"
+    eq = o_nh.equal(o_ref)
+    assert all(eq.values()), f"no-hit-outputs leg ({abi.plan_names(plan)}): {eq}\n{_diff_report(o_nh, o_ref)}"
     return o_gpu, cref
 
 
