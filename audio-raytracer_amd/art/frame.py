@@ -282,6 +282,16 @@ class Context:
             self._raise(rc)
         return int(bits.value)
 
+    def debug_echo_decided(self) -> tuple[int, int]:
+        """(replayed, traversed): the last frame's bounce-0 echo rays decided from the nearest cast's leaf
+        records and by the echo traversal (art_debug_echo_decided; diagnostics, synchronizes). (0, 0)
+        unless the frame ran the one-hit fused plan on an OBB-free scene without the counting instantiations."""
+        rep, trav = C.c_uint64(), C.c_uint64()
+        rc = self.lib.art_debug_echo_decided(self.ptr, C.byref(rep), C.byref(trav))
+        if rc:
+            self._raise(rc)
+        return int(rep.value), int(trav.value)
+
     def launch_device(self, d_origins: int, fan_count: int, d_block: int, out_flags: int = 0, stream: int | None = None):
         rc = self.lib.art_launch_device(self.ptr, d_origins, fan_count, d_block, out_flags, stream)
         if rc:

@@ -43,8 +43,9 @@ namespace {
 // art_debug_leaf_order, ART_CTX_GRAPH removed — a growth 2.3 should have made a major bump; 3.0:
 // art_kernel_times per kernel family (kernel_ms / kernel_launches / kernel_marks_dropped, 80 B),
 // ART_CTX_TIME_EACH_KERNEL.
-// 3.1: ART_CTX_EVENT_EACH_LAUNCH, art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*
-constexpr uint32_t kAbiVersion = (3u << 16) | 2u;
+// 3.1: ART_CTX_EVENT_EACH_LAUNCH, art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*;
+// 3.3: art_debug_echo_decided
+constexpr uint32_t kAbiVersion = (3u << 16) | 3u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -626,6 +627,24 @@ ART_API int art_debug_last_plan(art_ctx* c, uint32_t* bits) {
   if (!c || !bits) return ART_E_INVALID;
   if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
   *bits = c->devs.empty() ? 0u : c->devs[0].last_plan;
+  return ART_OK;
+}
+
+ART_API int art_debug_echo_decided(art_ctx* c, uint64_t* replayed, uint64_t* traversed) {
+  if (!c || !replayed || !traversed) return ART_E_INVALID;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
+  *replayed = *traversed = 0;
+  for (Device& dv : c->devs) {
+    if (!dv.echo_decided) continue;
+    unsigned long long v[kEchoCountSlots];
+    HIP_TRY(c, hipSetDevice(dv.id));
+    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipMemcpy(v, dv.echo_decided, sizeof v, hipMemcpyDeviceToHost));
+    for (unsigned long long x : v) {
+      *replayed += x & 0xffffffffull;
+      *traversed += x >> 32;
+    }
+  }
   return ART_OK;
 }
 

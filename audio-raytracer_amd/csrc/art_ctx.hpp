@@ -155,6 +155,7 @@ struct Device {
   LaunchFence fence;
   uint64_t exec_launches = 0;
   uint32_t last_plan = 0;  // ART_PLAN_* bits of the last frame's throughput raytrace stage (art_debug_last_plan)
+  const unsigned long long* echo_decided = nullptr;  // device: the last frame's echo replay counts (art_debug_echo_decided)
   int fan_begin = 0, fan_count = 0;
   size_t in_off = 0;  // art_schedule: this shard's [origins | permeation slots] in the input staging
   DevScene sc{};

@@ -59,8 +59,9 @@ static void raytrace_fast(Device& dv, const Frame& f, const FrameParams& fp, con
     fpc.S = std::min(chunk, fan_count - b0);
     dv.last_plan |= launch_raytrace_fast(dv.sc, fpc, f.L, d_origins + 3 * (size_t)b0, d_block + (size_t)b0 * f.L.stride,
                                          acc + (size_t)b0 * (size_t)f.TC * f.T, order, dv.pairs.p, pair_count, st, dv.echo,
-                                         marks.cap ? &marks : nullptr);
+                                         marks.cap ? &marks : nullptr, b0 == 0);
   }
+  dv.echo_decided = reinterpret_cast<const unsigned long long*>(pair_count + 4);
   for (int k = 0; k < marks.used; ++k)  // pool index base + 2 k
     dv.ev_used.push_back({kEvKernel0 + mkind[(size_t)k], dv.ev_used.size() * 2});
   dv.marks_dropped += marks.dropped;
@@ -80,11 +81,12 @@ int enqueue_kernels(art_ctx* c, Device& dv, const Frame& f, const float* d_origi
   const uint8_t* muffle_reset = raw + f.off_reset;
   const bool fast = (f.stages & ART_STAGE_RAYTRACE) && !count && !(c->flags & ART_CTX_FORCE_REFERENCE_ORDER);
   dv.last_plan = 0;  // (raytrace_fast sets it)
+  dv.echo_decided = nullptr;
   const size_t acc_per_fan = (size_t)f.TC * f.T;
   // muffle accumulators, then (16-B aligned) the visibility pair counters: cleared by the first
   // nearest_first_kernel of each fast-path chunk, by one memset before the reference-order kernel
   const size_t acc_words = ((size_t)fan_count * acc_per_fan + 3) & ~(size_t)3;
-  const size_t acc_bytes = acc_words * sizeof(uint32_t) + 16;  // + 4 pair counters
+  const size_t acc_bytes = acc_words * sizeof(uint32_t) + 16 + 8 * kEchoCountSlots;  // + 4 pair counters + the echo replay's counts
   if (!dv.acc.reserve(acc_bytes)) return fail(c, ART_E_NOMEM, "device allocation failed");
   uint32_t* acc = static_cast<uint32_t*>(dv.acc.p);
   uint32_t* pair_count = acc + acc_words;

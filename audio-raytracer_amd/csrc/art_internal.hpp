@@ -268,9 +268,14 @@ struct KernelMarks {
   int dropped = 0;           // launches that found no pair left (their family's time is then incomplete)
 };
 // Returns the launch plan it took as ART_PLAN_* bits (art_device.h; 0 for an empty chunk).
+// pair_count: 4 pair counters, then kEchoCountSlots 64-bit partial counts of the one-hit fused plan's
+// echo rays decided by leaf replay (low word) and by traversal (high word) (art_debug_echo_decided),
+// cleared by the frame's first chunk and counted on by the later ones.
+constexpr int kEchoCountSlots = 256;
 uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins,
                               uint8_t* block, uint32_t* muffle_acc, const int* ray_order, void* pair_buf,
-                              uint32_t* pair_count, hipStream_t st, const SideStream& echo, KernelMarks* marks = nullptr);
+                              uint32_t* pair_count, hipStream_t st, const SideStream& echo, KernelMarks* marks = nullptr,
+                              bool first_chunk = true);
 void launch_permeate(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins,
                      uint8_t* block, const int2* slot_batch, hipStream_t st);
 // (the collider sweep of every loss ray, art_kernels.hip: the reference-order and counting frames)

@@ -110,6 +110,41 @@ __device__ __forceinline__ bool force_all(const Seg& s, float om) {
          (s.d.x == 0.0f && s.d.y == 0.0f && s.d.z == 0.0f);
 }
 
+// Bounce-0 echo replay (one-hit fused plan): the bounce-0 nearest cast
+// (nearest_first_kernel<..., LOG>) logs the leaves it tests for each ray, with node margins wide
+// enough that every collider the ray's echo test can report lies in a logged leaf; the echo waves of
+// echo_muffle_kernel then test those leaves' slots against the echo segment instead of traversing.
+// A ray's record is 16 u16: [0] the number of logged leaves or kLogTraverse, [1 ..] kLogK leaf ids.
+// A ray keeps the echo traversal (kLogTraverse) when its log overflowed, when its direction or origin
+// is degenerate (force_all), or when its hit lies past the distance the margins were sized for:
+// best * |d|_1 > kLogCapFrac * the L1 diagonal of the BVH root's box.
+constexpr int kLogK = 15;
+constexpr uint32_t kLogTraverse = 0xffffu;
+#ifndef ART_LOG_CAP_FRAC
+#define ART_LOG_CAP_FRAC 0.3f
+#endif
+constexpr float kLogCapFrac = ART_LOG_CAP_FRAC;
+#ifndef ART_LOG_STEP_MARGIN
+#define ART_LOG_STEP_MARGIN 0  // (1: the table-less logging cast sizes each node test's margin by min(bound * |d|_1, cap), for A/B runs)
+#endif
+struct EchoLog {
+  uint16_t* rec;              // [ray slots][16]; nullptr: no log, every echo ray traverses
+  // echo rays decided by replay (low word) | by traversal (high word): kEchoCountSlots partial sums, an
+  // echo wave adds to the slot of its workgroup index (one shared counter serialized the frame's
+  // 8192 atomics: echo_muffle_kernel 47 -> 141 us at config 2); cleared by the frame's first cast
+  unsigned long long* count;
+  int keep_count;             // a later fan chunk of the frame: the counts go on
+};
+// The logging cast's margin operand for a ray (O, d) in place of |O|_1 (node_entry's om), and the cap
+// xcap on best * |d|_1 it covers: 1.05 |O|_1 + 4 |d|_1 + 0.4 xcap (replay).
+__device__ __forceinline__ float log_margin_om(const DevScene& sc, vec3 O, float d1, float& xcap, float* base = nullptr) {
+  const CullRec root = ldc(sc.bvh, 0);
+  xcap = kLogCapFrac * ((root.hix - root.lox) + (root.hiy - root.loy) + (root.hiz - root.loz));
+  const float b = 1.05f * (fabsf(O.x) + fabsf(O.y) + fabsf(O.z)) + 4.0f * d1;
+  if (base) *base = b;
+  return b + 0.4f * xcap;
+}
+
 // The widened box of a BVH node / collider (margin factor * (scale + om)):
 // entry distance of the segment, or false when it misses the box.
 __device__ __forceinline__ bool node_entry(const Seg& s, const CullRec& r, float om, float& tn) {
@@ -299,6 +334,25 @@ __device__ __forceinline__ bool leaf_slot_test(const Seg& s, const BvhRes& br, i
   return hit;
 }
 
+// leaf_slot_test<false> on a slot already fetched (qa, qb: its 32 B), the same operations.
+__device__ __forceinline__ bool leaf_rec_test(const Seg& s, float4 qa, float4 qb, float& dist, int& tid, unsigned* nt) {
+  const int cc = __float_as_int(qb.w);
+  dist = 0.0f;
+  tid = kNoOwner;
+  if (cc < 0) return false;  // empty slot past the last collider
+  tid = __float_as_int(qb.z);
+  if ((cc >> 28) == 0) {
+    SphereRec r;
+    r.cx = qa.x; r.cy = qa.y; r.cz = qa.z; r.r2 = qa.w;
+    ++nt[0];
+    return sphere_hit_dist(s, r, dist);
+  }
+  AabbRec r;
+  r.mnx = qa.x; r.mny = qa.y; r.mnz = qa.z; r.mxx = qa.w; r.mxy = qb.x; r.mxz = qb.y;
+  ++nt[1];
+  return aabb_test<false>(s, r, dist);
+}
+
 // Population count of a 64-bit lane mask as two 32-bit counts: an int result that compares with
 // 32-bit scalar / vector compares (a 64-bit count compares with VALU 64-bit compares).
 __device__ __forceinline__ int pop64(unsigned long long x) {
@@ -375,10 +429,14 @@ __device__ __forceinline__ unsigned long long nearest_key(float d, int code) {
 // TAB: every ray of the workgroup starts at one origin (a fan's bounce-0 casts), and `tab` holds
 // each BVH node's widened box relative to it (node_table): a node test is 6 multiplies and the
 // min / max, with the same operands as node_entry's.
-template <bool EX, bool OBB, bool PERM = false, bool TAB = false>
+// LOG: every leaf a quad tests is appended to its ray's log (s_log = the wave's 16 records of 16 u16,
+// s_lcnt = their counters; a thief appends to the home ray's), and the node margins use
+// log_margin_om (the echo replay above).
+template <bool EX, bool OBB, bool PERM = false, bool TAB = false, bool LOG = false>
 __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, bool alive, int lane, uint32_t* my,
                                                   int* s_bound, unsigned long long* s_key, float& best, int& code,
-                                                  unsigned long long* ex, const NodeTab* tab = nullptr) {
+                                                  unsigned long long* ex, const NodeTab* tab = nullptr,
+                                                  uint16_t* s_log = nullptr, int* s_lcnt = nullptr) {
   const int qd = lane & 3, wq = lane >> 2;
   uint32_t* const s_wave = my - wq * kBvhStack;
   best = FLT_MAX;
@@ -387,6 +445,13 @@ __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, boo
   if (ART_NEAREST_STEAL && qd == 0) s_key[wq] = ~0ull;  // the ray's shared result key, opened before the loop
   unsigned nt[3] = {0u, 0u, 0u}, nnode = 0;
   float om = fabsf(s.o.x) + fabsf(s.o.y) + fabsf(s.o.z);
+  constexpr bool kStepMargin = LOG && !TAB && ART_LOG_STEP_MARGIN;
+  float xcap = 0.0f, om_base = 0.0f, d1 = 0.0f;
+  if (LOG) {
+    d1 = fabsf(s.d.x) + fabsf(s.d.y) + fabsf(s.d.z);
+    om = log_margin_om(sc, s.o, d1, xcap, &om_base);
+    if (qd == 0) s_lcnt[wq] = 0;
+  }
   bool force = force_all(s, om);
   // the forced lanes as a lane mask (wave-uniform, kept in SGPRs): a node test ORs it in with scalar
   // instructions (__builtin_amdgcn_inverse_ballot_w64) instead of a per-lane 0/1 value
@@ -420,7 +485,8 @@ __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, boo
       h = node_entry_tab(s, tab, c0 + qd, tn);
     } else {
       const CullRec r = load_node(br, c0 + qd);
-      h = node_entry(s, r, om, tn);
+      // (kStepMargin: the margin for hits up to the bound, which the final hit does not exceed)
+      h = node_entry(s, r, kStepMargin ? __builtin_fmaf(0.4f, fminf(lim * d1, xcap), om_base) : om, tn);
     }
     const float en = fmaxf(tn, 0.0f);
     const bool enter = __builtin_amdgcn_inverse_ballot_w64(fmk) | (h & (en <= lim));  // (empty nodes: art_bvh.hip cull_stored)
@@ -429,6 +495,10 @@ __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, boo
   };
   auto leaf_step = [&](int leaf) {
     ART_DIAG_STEP(nsteps);
+    if (LOG && qd == 0) {  // (one quad visits a node, so a ray's log holds a leaf once)
+      const int at = atomicAdd(s_lcnt + home, 1);
+      if (at < kLogK) s_log[home * 16 + 1 + at] = (uint16_t)(leaf - leaf0);
+    }
     int cc, tid;
     float dd;
     const bool h = leaf_slot_test<OBB, PERM>(s, br, (leaf - leaf0) * kBvhLeaf + qd, cc, dd, tid, nt, sc.obbc);
@@ -489,6 +559,10 @@ __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, boo
           home = dhome;
           s.o = mk3(ox, oy, oz); s.d = mk3(dx, dy, dz); s.inv = mk3(ix, iy, iz); s.a2 = da2;
           om = dom;
+          if (kStepMargin) {  // the home ray's margin terms, by its own expressions
+            d1 = fabsf(dx) + fabsf(dy) + fabsf(dz);
+            om_base = 1.05f * (fabsf(ox) + fabsf(oy) + fabsf(oz)) + 4.0f * d1;
+          }
           force = dforce != 0;
           lim = dlim;
           mykey = ~0ull;  // (the finished ray's result went to its key above)
@@ -668,16 +742,22 @@ __device__ __forceinline__ void fold_path(const DevScene& sc, const FrameParams&
 // 1024 lanes, the 4 consecutive 64-ray groups of one fan, all rays at the fan origin, traverse with
 // the shared-origin node table in LDS (node_table_build; 2 workgroups and 8 waves per SIMD per CU,
 // 70 KB of LDS each).
-template <bool EX, bool OBB, bool FOLD, bool TAB = false>
+// LOG (bounce 0 of the one-hit fused plan on OBB-free scenes, not EX / FOLD / TAB): the cast logs each ray's tested leaves for
+// the echo replay (EchoLog above; quad_nearest_core<..., LOG>) and stores the records beside the hits.
+template <bool EX, bool OBB, bool FOLD, bool TAB = false, bool LOG = false>
 __global__ __launch_bounds__(TAB ? 1024 : 256) __attribute__((amdgpu_waves_per_eu(kNearestWaves<EX, OBB>))) void nearest_first_kernel(
     DevScene sc, FrameParams fp, const float* __restrict__ origins, const int* __restrict__ ray_order,
     int2* __restrict__ hits, float4* __restrict__ state, int step, uint32_t* __restrict__ zero, uint32_t nzero,
-    uint32_t* __restrict__ counters, FanLayout L, uint8_t* __restrict__ block, VisPairs vp) {
+    uint32_t* __restrict__ counters, FanLayout L, uint8_t* __restrict__ block, VisPairs vp, EchoLog el) {
+  static_assert(!LOG || (!EX && !FOLD && !TAB && !OBB), "the logging cast is the plain bounce-0 cast of OBB-free scenes");
   constexpr int kGroupsPerWg = TAB ? 4 : 1;
   __shared__ uint32_t s_stk[kBvhStack * 64 * kGroupsPerWg];
   __shared__ int s_bound[64 * kGroupsPerWg];
   __shared__ unsigned long long s_key[64 * kGroupsPerWg];
   __shared__ std::conditional_t<TAB, NodeTab, int> s_tab;
+  __shared__ __attribute__((aligned(8))) uint16_t s_log[LOG ? 16 * 64 * kGroupsPerWg : 4];
+  __shared__ int s_lcnt[LOG ? 64 * kGroupsPerWg : 1];
+  if (step == 0 && el.count && !el.keep_count && blockIdx.x == 0 && threadIdx.x < kEchoCountSlots) el.count[threadIdx.x] = 0ull;
   ART_WAVE_TIMER(0);
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int nrb = (fp.R + 63) >> 6;
@@ -758,8 +838,9 @@ __global__ __launch_bounds__(TAB ? 1024 : 256) __attribute__((amdgpu_waves_per_e
 #ifdef ART_DIAG
   const unsigned long long t0 = clock64();
 #endif
-  quad_nearest_core<EX, OBB, false, TAB>(sc, make_seg(o, d), alive, lane, my, s_bound + 16 * w, s_key + 16 * w, best, code,
-                                         ex, TAB ? reinterpret_cast<const NodeTab*>(&s_tab) : nullptr);
+  quad_nearest_core<EX, OBB, false, TAB, LOG>(sc, make_seg(o, d), alive, lane, my, s_bound + 16 * w, s_key + 16 * w, best,
+                                              code, ex, TAB ? reinterpret_cast<const NodeTab*>(&s_tab) : nullptr,
+                                              s_log + 256 * (LOG ? w : 0), s_lcnt + 16 * (LOG ? w : 0));
   if (FOLD) {
     // The ray's state is fetched again rather than kept live across the traversal (a memory
     // clobber: the compiler may not reuse the values loaded before it): 64 VGPRs, no spills.
@@ -795,6 +876,28 @@ __global__ __launch_bounds__(TAB ? 1024 : 256) __attribute__((amdgpu_waves_per_e
   // widening it to a 64-bit offset before the loop, two more live VGPRs)
   asm volatile("" : "+v"(out));
   if ((lane & 3) == 0 && write) hits[out] = make_int2(__float_as_int(best), code);
+  if constexpr (LOG) {
+    // The ray's record: its leaves, or kLogTraverse for a ray the replay may not decide. The ray is
+    // fetched again rather than kept live across the traversal (as FOLD does above).
+    asm volatile("" ::: "memory");
+    const int qd = lane & 3, rq = 16 * w + (lane >> 2);  // the workgroup's ray
+    const int fan2 = g / nrb, sl = (g - fan2 * nrb) * 64 + rr;
+    const vec3 O = load3(origins, fan2), dd = load_dir(sc.dirs, sl < fp.R ? ray_order[sl] : 0);
+    const float d1 = fabsf(dd.x) + fabsf(dd.y) + fabsf(dd.z);
+    bool trav = true;
+    uint32_t cnt = 0u;
+    if (sc.bvh_levels > 0) {
+      float xcap;
+      const float om = log_margin_om(sc, O, d1, xcap);  // the cast's own operand, so the same forced rays
+      cnt = (uint32_t)s_lcnt[rq];
+      Seg sd;  // (force_all reads the direction only)
+      sd.o = O; sd.d = sd.inv = dd; sd.a2 = 0.0f;
+      trav = force_all(sd, om) || cnt > (uint32_t)kLogK || !(best * d1 <= xcap);
+    }
+    uint2 v = reinterpret_cast<const uint2*>(s_log)[rq * 4 + qd];
+    if (qd == 0) v.x = (v.x & 0xffff0000u) | (trav ? kLogTraverse : cnt);
+    if (write) reinterpret_cast<uint2*>(el.rec)[(size_t)out * 4 + qd] = v;
+  }
 #ifdef ART_DIAG
   if (lane == 0) diag_add(0, clock64() - t0);
 #endif
@@ -1213,10 +1316,16 @@ __device__ __forceinline__ bool quad_echo_core(const DevScene& sc, Seg s, float 
   return !((wblocked >> wq) & 1u);
 }
 
-template <bool OBB, bool HM>
+// REPLAY (HM, echo_muffle_kernel's non-counting OBB-free instantiation): a quad whose ray has a leaf record
+// (EchoLog, el.rec set: the nearest cast logged this frame) tests the record's leaves against the
+// echo segment, 4 slots per step, to its first blocker; the rays marked kLogTraverse run
+// quad_echo_core in the same wave, where the replaying quads are idle quads that share their work.
+// s_rec: the wave's 16 records in LDS.
+template <bool OBB, bool HM, bool REPLAY = false>
 __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs& vp, const uint32_t* count,
                                               unsigned long long* ex, uint32_t blk, int w, uint32_t* s_wave,
-                                              const uint32_t* ecnt, int bounce, uint8_t* block, const EchoFromHits& eh) {
+                                              const uint32_t* ecnt, int bounce, uint8_t* block, const EchoFromHits& eh,
+                                              const EchoLog* el = nullptr, uint16_t* s_rec = nullptr) {
   const int lane = threadIdx.x & 63, qd = lane & 3;
   const int wq = lane >> 2, slot = w * 16 + wq;                // segment of the block's 64-pair batch
   if (sc.bvh_levels == 0 && !HM) return;                       // no colliders: nothing blocks
@@ -1228,6 +1337,10 @@ __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs
   int owner = kNoOwner;
   s.o = s.d = s.inv = mk3(0.0f, 0.0f, 0.0f);
   s.a2 = 0.0f;
+  uint2 lrec = make_uint2(kLogTraverse, 0u);  // this lane's quarter of the ray's leaf record, fetched beside the hit
+  if constexpr (REPLAY) {
+    if (el->rec) lrec = reinterpret_cast<const uint2*>(el->rec)[((size_t)blk * 64 + (uint32_t)slot) * 4 + qd];
+  }
   if (HM) {
     bool slot_ok;
     valid = echo_seg_from_hit(sc, eh, blk, slot, s, maxd, out_at, out_val, slot_ok);
@@ -1272,7 +1385,49 @@ __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs
     }
   }
   unsigned nt[3] = {0u, 0u, 0u}, nnode = 0;
-  const bool visible = quad_echo_core<OBB, HM && ART_ECHO_PARK>(sc, s, maxd, owner, valid, lane, s_wave, nt, nnode);
+  bool replayed = false, blocked = false;  // quad-uniform
+  if constexpr (REPLAY) {
+    if (el->rec) {  // (wave-uniform)
+      reinterpret_cast<uint2*>(s_rec)[wq * 4 + qd] = lrec;
+      // (lanes read each other's LDS entries: order the writes before the reads, as permeate_bvh_kernel does)
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      const uint32_t n = s_rec[wq * 16];
+      replayed = valid && n <= (uint32_t)kLogK;  // (kLogTraverse: the echo traversal below)
+      const BvhRes br = bvh_res(sc);
+      const int qshift = lane & ~3;
+      // leaf j's slot of this lane (32 B: OBB-free scenes), fetched one step ahead of its test
+      auto fetch = [&](uint32_t j, float4& qa, float4& qb) {
+        const int at = ((int)s_rec[wq * 16 + 1 + j] * kBvhLeaf + qd) * 32;
+        qa = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(br.leaves, at, 0, 0));
+        qb = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(br.leaves, at + 16, 0, 0));
+      };
+      float4 na = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nb = na;
+      bool on = replayed && n > 0u;
+      if (on) fetch(0u, na, nb);
+      for (uint32_t j = 0; __any(on); ++j) {
+        const float4 qa = na, qb = nb;
+        const bool more = on && j + 1u < n;
+        if (more) fetch(j + 1u, na, nb);
+        bool blk_here = false;
+        if (on) {
+          int tid;
+          float d;
+          const bool hh = leaf_rec_test(s, qa, qb, d, tid, nt);
+          blk_here = hh && d < maxd && tid != owner;  // :373-394, quad_echo_core's test
+        }
+        blocked = blocked || ((uint32_t)(__builtin_amdgcn_ballot_w64(blk_here) >> qshift) & 0xFu) != 0u;
+        on = more && !blocked;
+      }
+    }
+    if (el->count) {
+      const uint32_t nr = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(replayed) & kQuad0);
+      const uint32_t nv = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid && !replayed) & kQuad0);
+      if (lane == 0) atomicAdd(el->count + (blockIdx.x & (kEchoCountSlots - 1)), (unsigned long long)nr | ((unsigned long long)nv << 32));
+    }
+  }
+  bool visible = quad_echo_core<OBB, HM && ART_ECHO_PARK>(sc, s, maxd, owner, valid && !replayed, lane, s_wave, nt, nnode);
+  if (REPLAY && replayed) visible = !blocked;
   if (HM) {
     if (valid && qd == 0) reinterpret_cast<uint16_t*>(block)[out_at] = visible ? out_val : (uint16_t)0;  // :76, :142-144
   } else if (vp.fixed) {
@@ -1638,8 +1793,9 @@ template <bool EX, bool OBB>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OBB ? (EX ? 5 : ART_ECHO_MUFFLE_OBB_WAVES) : kEchoWaves<EX, OBB>)))
 void echo_muffle_kernel(DevScene sc, FrameParams fp, VisPairs vp, const uint32_t* __restrict__ count,
                         unsigned long long* ex, uint8_t* __restrict__ block, EchoFromHits eh, uint32_t* __restrict__ acc,
-                        uint32_t groups, uint32_t mblocks, int mt) {
+                        uint32_t groups, uint32_t mblocks, int mt, EchoLog el) {
   __shared__ uint32_t s_stk[16 * kBvhStack];
+  __shared__ __attribute__((aligned(8))) uint16_t s_rec[EX || OBB ? 4 : 16 * 16];
   const uint32_t b = blockIdx.x;
   const uint32_t ne = 4u * groups;  // echo workgroups
   ART_WAVE_TIMER(b < ne ? 1u : 2u);
@@ -1660,7 +1816,7 @@ void echo_muffle_kernel(DevScene sc, FrameParams fp, VisPairs vp, const uint32_t
     uint32_t g;
     int w;
     split(b, groups, g, w);
-    vis_quad_body<OBB, true>(sc, vp, count, EX ? ex : nullptr, g, w, s_stk, nullptr, -1, block, eh);
+    vis_quad_body<OBB, true, !EX && !OBB>(sc, vp, count, EX ? ex : nullptr, g, w, s_stk, nullptr, -1, block, eh, &el, s_rec);
     return;
   }
   if (ART_MUFFLE_XCD == 2 && groups % 8u == 0u) {
@@ -1946,6 +2102,7 @@ void launch_permeate(const DevScene& sc, const FrameParams& fp, const FanLayout&
 struct PairBufs {
   VisPairs vp;
   int2* pre;        // [groups * 64] nearest hits of the current bounce
+  uint16_t* elog;   // [groups * 64][16] leaf records of the bounce-0 cast (one-hit frames with one batch slot: EchoLog)
   float4* state;    // [groups * 64][2] ray state between the bounce launches (multi-hit frames)
   size_t total;
 };
@@ -1967,6 +2124,7 @@ static PairBufs pair_bufs(void* base, const FrameParams& fp) {
   b.vp.hrec = reinterpret_cast<float4*>(take(hcap * 16));
   b.vp.echo_cap = (uint32_t)ecap;
   b.pre = reinterpret_cast<int2*>(take(slots * sizeof(int2)));
+  if (fp.H == 1 && fp.TC == 1) b.elog = reinterpret_cast<uint16_t*>(take(slots * 32));
   if (fp.H > 1) b.state = reinterpret_cast<float4*>(take(slots * (2 * sizeof(float4) + 4) + 2 * kLiveCounters * 4));
   b.total = off;
   return b;
@@ -2003,7 +2161,7 @@ static void marked(KernelMarks* marks, int kind, hipStream_t s, F&& launch) {
 
 uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const FanLayout& L, const float* origins,
                               uint8_t* block, uint32_t* muffle_acc, const int* ray_order, void* pair_buf, uint32_t* pair_count,
-                              hipStream_t st, const SideStream& echo, KernelMarks* marks) {
+                              hipStream_t st, const SideStream& echo, KernelMarks* marks, bool first_chunk) {
   if (fp.S == 0) return 0;
   const unsigned groups = (unsigned)((size_t)fp.S * ((fp.R + 63) / 64));
   const bool obb = sc.no > 0;  // OBB-free scenes run instantiations without the OBB tests
@@ -2082,18 +2240,35 @@ uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const F
 #endif
   const bool tab = ART_NEAREST_TAB && (ART_NEAREST_TAB == 2 || sc.no > 0) && ((fp.R + 63) / 64) % 4 == 0 &&
                    sc.bvh_levels > 0 && (long long)sc.bvh_leaf0 * 4 + 1 <= kTabNodes;
+  // The fused plan's bounce-0 cast logs the leaves it tests and the echo waves replay them (EchoLog;
+  // not the counting instantiations; leaf ids are 16-bit: up to 65536 leaves). OBB-free scenes only,
+  // by measurement: with OBBs the wider node margins cost the cast more than the echo
+  // waves save (config 3 0.1526 -> 0.1547 ms/step, config 4 1.019 -> 1.102).
+#ifndef ART_ECHO_REPLAY
+#define ART_ECHO_REPLAY 1  // (0: every echo ray traverses, for A/B runs)
+#endif
+  const bool logp = ART_ECHO_REPLAY && fused && !fp.exec && !obb && !tab && pb.elog && sc.bvh_levels > 0 &&
+                    3ll * sc.bvh_leaf0 + 1 <= 65536;
+  EchoLog el;
+  el.rec = logp ? pb.elog : nullptr;
+  el.count = pair_count ? reinterpret_cast<unsigned long long*>(pair_count + 4) : nullptr;  // (after the 4 pair counters)
+  el.keep_count = first_chunk ? 0 : 1;
   for (int k = 0; k < (multi ? fp.H : 1); ++k) {
 #define ART_NEAREST(EX_, OBB_, F_)                                                                                  \
   do {                                                                                                              \
     if (tab && k == 0)                                                                                              \
       hipLaunchKernelGGL((nearest_first_kernel<EX_, OBB_, F_, true>), dim3(groups / 4), dim3(1024), 0, st, sc, fp, origins, \
-                         ray_order, pb.pre, pb.state, k, muffle_acc, nacc, pair_count, L, block, pb.vp);           \
+                         ray_order, pb.pre, pb.state, k, muffle_acc, nacc, pair_count, L, block, pb.vp, el);       \
     else                                                                                                            \
       hipLaunchKernelGGL((nearest_first_kernel<EX_, OBB_, F_>), dim3(groups), dim3(256), 0, st, sc, fp, origins, ray_order,  \
-                         pb.pre, pb.state, k, muffle_acc, k == 0 ? nacc : 0u, k == 0 ? pair_count : nullptr, L, block, pb.vp); \
+                         pb.pre, pb.state, k, muffle_acc, k == 0 ? nacc : 0u, k == 0 ? pair_count : nullptr, L, block, pb.vp, el); \
   } while (0)
+
     marked(marks, kMarkNearest, st, [&] {
-      if (fold) {
+      if (logp && k == 0) {
+        hipLaunchKernelGGL((nearest_first_kernel<false, false, false, false, true>), dim3(groups), dim3(256), 0, st, sc, fp,
+                           origins, ray_order, pb.pre, pb.state, k, muffle_acc, nacc, pair_count, L, block, pb.vp, el);
+      } else if (fold) {
         if (fp.exec) { if (obb) ART_NEAREST(true, true, true); else ART_NEAREST(true, false, true); }
         else { if (obb) ART_NEAREST(false, true, true); else ART_NEAREST(false, false, true); }
       } else {
@@ -2127,7 +2302,7 @@ uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const F
 #define ART_ECHO_MUFFLE(EX_, OBB_)                                                                                    \
   hipLaunchKernelGGL((echo_muffle_kernel<EX_, OBB_>), dim3(4 * (groups + mblocks * mt)), dim3(64), 0, \
                      st, sc, fp, pb.vp,   \
-                     pair_count, EX_ ? fp.exec : nullptr, block, eh, muffle_acc, groups, mblocks, (int)mt)
+                     pair_count, EX_ ? fp.exec : nullptr, block, eh, muffle_acc, groups, mblocks, (int)mt, el)
     marked(marks, kMarkEchoMuffle, st, [&] {
       if (fp.exec) { if (obb) ART_ECHO_MUFFLE(true, true); else ART_ECHO_MUFFLE(true, false); }
       else { if (obb) ART_ECHO_MUFFLE(false, true); else ART_ECHO_MUFFLE(false, false); }

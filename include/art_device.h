@@ -160,6 +160,14 @@ ART_API int art_debug_leaf_order(art_ctx* ctx, uint32_t* out, int32_t cap);
 #define ART_PLAN_CHUNKED    0x100u /* more than one fan chunk */
 ART_API int art_debug_last_plan(art_ctx* ctx, uint32_t* bits);
 
+/* Diagnostics (tests, ABI 3.3): how the bounce-0 echo rays of the most recent frame were decided,
+ * summed over the context's devices and the frame's fan chunks. The one-hit fused plan
+ * (ART_PLAN_FUSED without ART_PLAN_EX and ART_PLAN_OBB) decides an echo ray by testing the leaves its nearest cast
+ * logged (replayed) or, for a ray whose log overflowed, whose hit lies past the logging margins' reach
+ * or whose direction or origin is degenerate, by the echo traversal (traversed); every other plan
+ * reports 0 and 0. Synchronizes. */
+ART_API int art_debug_echo_decided(art_ctx* ctx, uint64_t* replayed, uint64_t* traversed);
+
 /* Context over an explicit list of HIP devices: fans of every art_schedule are sharded
  * contiguously over the list (one HIP stream, one scene copy and one set of buffers per entry).
  * An id may repeat: art_create_on({0, 0, 0}, 3, &ctx) runs the in-process multi-device split and
