@@ -52,6 +52,7 @@ ART_CTX_COUNT_EXECUTED = 0x10
 ART_CTX_RESIDENT_COLLIDERS = 0x20  # art_colliders.h
 ART_CTX_TIME_EACH_KERNEL = 0x200
 ART_CTX_EVENT_EACH_LAUNCH = 0x400  # art_launch_device records its completion event (the caller may drop its stream)
+ART_CTX_RESIDENT_TARGETS = 0x800  # art_colliders.h: positions and T come from the last art_targets_sync
 # art_debug_last_plan: the launch plan of the throughput raytrace stage (art_device.h)
 ART_PLAN_FUSED, ART_PLAN_HM, ART_PLAN_SPLIT, ART_PLAN_FOLD, ART_PLAN_PER_BOUNCE = 0x1, 0x2, 0x4, 0x8, 0x10
 ART_PLAN_TAB, ART_PLAN_OBB, ART_PLAN_EX, ART_PLAN_CHUNKED = 0x20, 0x40, 0x80, 0x100
@@ -134,6 +135,11 @@ KERNEL_FAMILIES = ("nearest_first_kernel", "echo_muffle_kernel", "vis_kernel", "
 class art_collider_sync_stats(C.Structure):
     _fields_ = [("dirty_records", C.c_int32), ("full_prep", C.c_int32), ("reallocated", C.c_int32),
                 ("cells_rebuilt", C.c_int32), ("bytes_uploaded", C.c_uint64)]
+
+
+class art_target_sync_stats(C.Structure):
+    _fields_ = [("dirty_targets", C.c_int32), ("count_changed", C.c_int32), ("lists_rebuilt", C.c_int32),
+                ("lists_full_rebuild", C.c_int32), ("bytes_uploaded", C.c_uint64)]
 
 
 class art_exec_kernel(C.Structure):
@@ -237,6 +243,17 @@ SIGNATURES = {
     "art_colliders_clear": (I32, [VP]),
     "art_colliders_sync": (I32, [VP]),
     "art_colliders_last_sync": (I32, [VP, C.POINTER(art_collider_sync_stats)]),
+    "art_target_add": (I32, [VP, VP, C.POINTER(I32)]),
+    "art_target_set": (I32, [VP, I32, VP]),
+    "art_target_set_many": (I32, [VP, VP, VP, I32]),
+    "art_target_remove_swapback": (I32, [VP, I32]),
+    "art_target_get": (I32, [VP, I32, VP]),
+    "art_target_count": (I32, [VP]),
+    "art_target_synced_count": (I32, [VP]),
+    "art_targets_clear": (I32, [VP]),
+    "art_targets_sync": (I32, [VP]),
+    "art_targets_last_sync": (I32, [VP, C.POINTER(art_target_sync_stats)]),
+    "art_debug_cells_arena": (I32, [VP, C.POINTER(U64), C.POINTER(U64), C.POINTER(U32)]),
     "art_device_count": (I32, []),
     "art_create_on": (I32, [C.POINTER(I32), I32, C.POINTER(VP)]),
     # art_synth.h

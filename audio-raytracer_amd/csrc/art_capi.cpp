@@ -44,8 +44,9 @@ namespace {
 // art_kernel_times per kernel family (kernel_ms / kernel_launches / kernel_marks_dropped, 80 B),
 // ART_CTX_TIME_EACH_KERNEL.
 // 3.1: ART_CTX_EVENT_EACH_LAUNCH, art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*;
-// 3.3: art_debug_echo_decided
-constexpr uint32_t kAbiVersion = (3u << 16) | 3u;
+// 3.3: art_debug_echo_decided; 3.4: the resident target store (art_target_*, art_targets_*,
+// ART_CTX_RESIDENT_TARGETS, art_debug_cells_arena)
+constexpr uint32_t kAbiVersion = (3u << 16) | 4u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -76,6 +77,23 @@ int check_resident(art_ctx* c, const art_frame_desc* d) {
   if (d->sphere_count || d->aabb_count || d->obb_count || d->sphere_colliders || d->aabb_colliders || d->obb_colliders)
     return fail(c, ART_E_INVALID, "ART_CTX_RESIDENT_COLLIDERS: the desc's collider arrays must be NULL / 0");
   if (!c->store.store_synced) return fail(c, ART_E_STATE, "ART_CTX_RESIDENT_COLLIDERS: no art_colliders_sync yet");
+  return ART_OK;
+}
+
+// ART_CTX_RESIDENT_TARGETS: the desc carries no targets and the store has been synced; the frame
+// is then made from `eff`, the desc with the positions and count of the last art_targets_sync (d
+// points at it). Without the flag d stays.
+int resident_targets_desc(art_ctx* c, const art_frame_desc*& d, art_frame_desc& eff) {
+  if (!(c->flags & ART_CTX_RESIDENT_TARGETS)) return ART_OK;
+  if (!d) return fail(c, ART_E_INVALID, "desc is NULL");
+  if (d->audio_target_positions || d->audio_target_count)
+    return fail(c, ART_E_INVALID, "ART_CTX_RESIDENT_TARGETS: the desc's audio_target_positions / count must be NULL / 0");
+  if (!c->targets.store_synced) return fail(c, ART_E_STATE, "ART_CTX_RESIDENT_TARGETS: no art_targets_sync yet");
+  eff = *d;
+  eff.audio_target_positions = c->targets.snap.data();
+  eff.audio_target_count = c->targets.synced;  // (0: validate_desc refuses a frame without targets)
+  if (c->targets.synced == 0) eff.audio_target_positions = nullptr;
+  d = &eff;
   return ART_OK;
 }
 
@@ -224,7 +242,8 @@ ART_API void art_destroy(art_ctx* c) {
       dv.fence.pending = false;
     }
     dv.raw.release(); dv.soa.release(); dv.origins.release(); dv.block.release(); dv.acc.release(); dv.counts.release();
-    dv.exec.release(); dv.pairs.release(); dv.dsp.release(); dv.cones.release();
+    dv.exec.release(); dv.pairs.release(); dv.dsp.release(); dv.cones.release(); dv.tsel.release();
+    dv.cell_status.release();
     dv.store.raw.release(); dv.store.soa.release(); dv.store.upd.release();
     if (dv.store.done) (void)hipEventDestroy(dv.store.done);
     for (hipEvent_t e : dv.store.epoch)
@@ -286,7 +305,10 @@ ART_API int art_schedule(art_ctx* c, const art_frame_desc* d, const art_fan* fan
   if (!c) return ART_E_INVALID;
   if (!out) return fail(c, ART_E_INVALID, "handle pointer is NULL");
   if (c->inflight) return fail(c, ART_E_STATE, "a frame is in flight: call art_complete first (AudioRayTracer.cs:97)");
-  int rc = validate_desc(c, d);
+  art_frame_desc eff;
+  int rc = resident_targets_desc(c, d, eff);
+  if (rc) return rc;
+  rc = validate_desc(c, d);
   if (rc) return rc;
   if (fan_count < 0 || (fan_count > 0 && !fans)) return fail(c, ART_E_INVALID, "bad fans array");
   rc = check_resident(c, d);
@@ -316,7 +338,8 @@ ART_API int art_schedule(art_ctx* c, const art_frame_desc* d, const art_fan* fan
   }
   PhaseClock pc(&c->hp);
   Frame& f = c->fr;
-  make_frame(d, hits ? ART_OUT_HIT_RESULTS : 0u, f, (c->flags & ART_CTX_RESIDENT_COLLIDERS) ? c->store.synced : nullptr);
+  make_frame(d, hits ? ART_OUT_HIT_RESULTS : 0u, f, (c->flags & ART_CTX_RESIDENT_COLLIDERS) ? c->store.synced : nullptr,
+             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0);
   const FanLayout& L = f.L;
   const size_t origins_off = align_up(f.raw_bytes, 16);
   if (!c->h_block.reserve((size_t)fan_count * L.stride)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
@@ -484,12 +507,16 @@ ART_API int art_scene_bind(art_ctx* c, const art_frame_desc* d) {
   if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
   // the in-flight frame's art_complete reads c->fr and its H2D copy may still read c->h_in
   if (c->inflight) return fail(c, ART_E_STATE, "art_scene_bind: a frame is in flight (bind after art_complete)");
-  int rc = validate_desc(c, d);
+  art_frame_desc eff;
+  int rc = resident_targets_desc(c, d, eff);
+  if (rc) return rc;
+  rc = validate_desc(c, d);
   if (rc) return rc;
   rc = check_resident(c, d);
   if (rc) return rc;
   Frame& f = c->fr;
-  make_frame(d, 0u, f, (c->flags & ART_CTX_RESIDENT_COLLIDERS) ? c->store.synced : nullptr);
+  make_frame(d, 0u, f, (c->flags & ART_CTX_RESIDENT_COLLIDERS) ? c->store.synced : nullptr,
+             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0);
   if (!c->h_in.reserve(f.raw_bytes)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
   pack_inputs(d, f, static_cast<uint8_t*>(c->h_in.p));
   count_nonowned(c, d);
@@ -520,7 +547,7 @@ static int launch_common(art_ctx* c, const float* d_origins, int32_t fan_count, 
     f.L = make_layout(&tmp, out_flags);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);  // NULL is the HIP default stream (torch's default)
-  if (f.resident && dv.store.done && st != dv.store.stream) HIP_TRY(c, hipStreamWaitEvent(st, dv.store.done, 0));
+  if ((f.resident || f.res_targets) && dv.store.done && st != dv.store.stream) HIP_TRY(c, hipStreamWaitEvent(st, dv.store.done, 0));
   // frames share the context's accumulators and pair buffers: a launch on another stream than the
   // previous one waits for it (on the same stream, stream order already does)
   if (dv.fence.pending && st != dv.fence.stream) {
@@ -645,6 +672,21 @@ ART_API int art_debug_echo_decided(art_ctx* c, uint64_t* replayed, uint64_t* tra
       *traversed += x >> 32;
     }
   }
+  return ART_OK;
+}
+
+ART_API int art_debug_cells_arena(art_ctx* c, uint64_t* used, uint64_t* cap, uint32_t* dropped_targets) {
+  if (!c || !used || !cap || !dropped_targets) return ART_E_INVALID;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
+  if (c->devs.empty() || !c->devs[0].bound) return fail(c, ART_E_STATE, "no scene bound (art_scene_bind)");
+  Device& dv = c->devs[0];
+  HIP_TRY(c, hipSetDevice(dv.id));
+  HIP_TRY(c, hipDeviceSynchronize());
+  uint32_t v[2] = {0u, 0u};
+  if (dv.cb.tail) HIP_TRY(c, hipMemcpy(v, dv.cb.tail, sizeof v, hipMemcpyDeviceToHost));
+  *used = v[0];
+  *cap = dv.cb.cap;
+  *dropped_targets = v[1];
   return ART_OK;
 }
 

@@ -133,40 +133,52 @@ struct alignas(16) CellGeo {
   uint32_t pad[2];
 };
 
-// Each pair's face rectangles also as one packed word per (target, face, collider), after the T * n
+// The passes work on K targets by rank: every target in a full build (sel == nullptr, K = T), the
+// selected ones in a partial build (launch_build_cells_targets). The CellGeo scratch is indexed by
+// rank (K x n), the counters, starts and per-target words by the target itself.
+__device__ __forceinline__ int sel_target(const int* __restrict__ sel, int r) { return sel ? sel[r] : r; }
+
+// Each pair's face rectangles also as one packed word per (rank, face, collider), after the K * n
 // CellGeo records: the row passes read 4 coalesced bytes per item and fetch the 64-B record only
 // for the rows the rectangle covers.
-__device__ __forceinline__ uint32_t* cell_rects(CellGeo* geo, int T, int n) {
-  return reinterpret_cast<uint32_t*>(geo + (size_t)T * n);
+__device__ __forceinline__ uint32_t* cell_rects(CellGeo* geo, int K, int n) {
+  return reinterpret_cast<uint32_t*>(geo + (size_t)K * n);
 }
-__device__ __forceinline__ void cell_rects_write(CellGeo* geo, int T, int n, int t, int g, const CellGeo& G) {
-  uint32_t* r = cell_rects(geo, T, n);
+__device__ __forceinline__ void cell_rects_write(CellGeo* geo, int K, int n, int r, int g, const CellGeo& G) {
+  uint32_t* w = cell_rects(geo, K, n);
   for (int f = 0; f < 6; ++f)
-    r[((size_t)t * 6 + f) * n + g] = (uint32_t)G.rect[f][0] | ((uint32_t)G.rect[f][1] << 8) | ((uint32_t)G.rect[f][2] << 16) |
+    w[((size_t)r * 6 + f) * n + g] = (uint32_t)G.rect[f][0] | ((uint32_t)G.rect[f][1] << 8) | ((uint32_t)G.rect[f][2] << 16) |
                                      ((uint32_t)G.rect[f][3] << 24);
 }
 
-// One work-item per (target, collider), and per (target, cell, type) counter (zeroed, with the
-// sentinel); the first T also set each target's segment bound, list flag and entry total.
+// One work-item per (rank, collider), and per (target, cell, type) counter of the K targets (zeroed,
+// pads included; a full build also zeroes the sentinel); the first K also set each target's segment
+// bound, list flag and entry total.
 // (grid-stride: one launch stays far below HIP's 2^32 work-item limit)
-__device__ void cells_geo_one(const DevScene& sc, const CellBufs& cb, int n, int T, long long k, CellGeo* __restrict__ geo);
-__global__ __launch_bounds__(256) void cells_geo_kernel(DevScene sc, CellBufs cb, int T, CellGeo* __restrict__ geo,
-                                                        uint32_t counters) {
+__device__ void cells_geo_one(const DevScene& sc, const CellBufs& cb, int n, int K, int t, long long k, CellGeo* __restrict__ geo);
+__global__ __launch_bounds__(256) void cells_geo_kernel(DevScene sc, CellBufs cb, const int* __restrict__ sel, int K,
+                                                        CellGeo* __restrict__ geo) {
   const int n = sc.ns + sc.na + sc.no;
-  const long long items = std::max((long long)n * T, (long long)counters);
+  const long long counters = (long long)K * kCellStride;
+  const long long items = std::max((long long)n * K, counters + 1);
   for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < items; k += (long long)gridDim.x * blockDim.x) {
-    if (k < counters) cb.count[k] = 0u;
-    if (k < T) {
-      const float v = cells_far_t(sc, cb, (int)k);
-      cb.far[k] = v;
-      cb.ok[k] = isfinite(v) ? 1u : 0u;
-      cb.tcount[k] = 0ull;
+    if (k < counters) {
+      const int r = (int)(k / kCellStride);
+      cb.count[(size_t)sel_target(sel, r) * kCellStride + (size_t)(k - (long long)r * kCellStride)] = 0u;
     }
-    if (k < (long long)n * T) cells_geo_one(sc, cb, n, T, k, geo);
+    if (k == counters && !sel) cb.count[counters] = 0u;
+    if (k < K) {
+      const int t = sel_target(sel, (int)k);
+      const float v = cells_far_t(sc, cb, t);
+      cb.far[t] = v;
+      cb.ok[t] = isfinite(v) ? 1u : 0u;
+      cb.tcount[t] = 0ull;
+    }
+    if (k < (long long)n * K) cells_geo_one(sc, cb, n, K, sel_target(sel, (int)(k / n)), k, geo);
   }
 }
-__device__ void cells_geo_one(const DevScene& sc, const CellBufs& cb, int n, int T, long long k, CellGeo* __restrict__ geo) {
-  const int t = (int)(k / n), g = (int)(k - (long long)t * n);
+__device__ void cells_geo_one(const DevScene& sc, const CellBufs& cb, int n, int K, int t, long long k, CellGeo* __restrict__ geo) {
+  const int r_ = (int)(k / n), g = (int)(k - (long long)r_ * n);
   CellGeo G;
   for (int f = 0; f < 6; ++f) { G.rect[f][0] = 1; G.rect[f][1] = 0; G.rect[f][2] = 1; G.rect[f][3] = 0; }
   G.pad[0] = G.pad[1] = 0u;
@@ -178,7 +190,7 @@ __device__ void cells_geo_one(const DevScene& sc, const CellBufs& cb, int n, int
   G.ux = G.uy = G.uz = G.sb = G.cb = G.near = 0.0f;
   // owned by the target (its muffle rays skip it, :413, :426, :439) or no lists: no cells
   const float far = cells_far_t(sc, cb, t);  // (cb.far[t], written by another work-item of this launch)
-  if (!isfinite(far) || tid == t) { geo[k] = G; cell_rects_write(geo, T, n, t, g, G); return; }
+  if (!isfinite(far) || tid == t) { geo[k] = G; cell_rects_write(geo, K, n, r_, g, G); return; }
   // The collider's bounding sphere and its error margin. Every test's rounding is relative to the
   // segment-start-to-collider vector (the operands o and the record are exact floats): a reported
   // blocking point lies within factor * (|o - c| + |h|_1) of the shape,
@@ -237,7 +249,7 @@ __device__ void cells_geo_one(const DevScene& sc, const CellBufs& cb, int n, int
     G.rect[f][0] = (uint8_t)i0; G.rect[f][1] = (uint8_t)i1; G.rect[f][2] = (uint8_t)j0; G.rect[f][3] = (uint8_t)j1;
   }
   geo[k] = G;
-  cell_rects_write(geo, T, n, t, g, G);
+  cell_rects_write(geo, K, n, r_, g, G);
 }
 
 // One workgroup per (target, face, cell row) and 256 colliders (grid-stride over these units): each
@@ -251,18 +263,20 @@ __device__ void cells_geo_one(const DevScene& sc, const CellBufs& cb, int n, int
 // (cells_block_scan_kernel). (Round 4 also measured one workgroup per (target, face): 128 + 256 us with
 // per-item load balancing over each wave — 32x fewer waves left every step's latency exposed.)
 template <bool FILL>
-__global__ __launch_bounds__(256) void cells_row_kernel(CellGeo* __restrict__ geo, int T, CellBufs cb, int n) {
+__global__ __launch_bounds__(256) void cells_row_kernel(CellGeo* __restrict__ geo, const int* __restrict__ sel, int K,
+                                                        CellBufs cb, int n) {
   __shared__ uint32_t s_cnt[kCellG * 3];
   __shared__ float4 s_cone[kCellG];  // axis, cos_a
   __shared__ float s_sin[kCellG];
   const int tid = threadIdx.x;
   const int chunks = (n + 255) >> 8;
-  const long long units = (long long)T * 6 * kCellG * chunks;
-  const uint32_t* rects = cell_rects(geo, T, n);
+  const long long units = (long long)K * 6 * kCellG * chunks;
+  const uint32_t* rects = cell_rects(geo, K, n);
   for (long long u = blockIdx.x; u < units; u += gridDim.x) {  // (workgroup-uniform)
     const long long row = u / chunks;
     const int gc = (int)(u - row * chunks);
-    const int t = (int)(row / (6 * kCellG)), fr = (int)(row - (long long)t * 6 * kCellG), f = fr / kCellG, j = fr - f * kCellG;
+    const int r = (int)(row / (6 * kCellG)), fr = (int)(row - (long long)r * 6 * kCellG), f = fr / kCellG, j = fr - f * kCellG;
+    const int t = sel_target(sel, r);  // (workgroup-uniform)
     if (FILL && !cb.ok[t]) continue;  // (workgroup-uniform: a dropped target's lists stay empty)
     const int g = gc * 256 + tid;
     if (tid < kCellG * 3) s_cnt[tid] = 0u;
@@ -271,13 +285,13 @@ __global__ __launch_bounds__(256) void cells_row_kernel(CellGeo* __restrict__ ge
       s_cone[tid] = make_float4(cc.ax, cc.ay, cc.az, cc.cos_a);
       s_sin[tid] = cc.sin_a;
     }
-    const uint32_t rc = g < n ? rects[((size_t)t * 6 + f) * n + g] : 0x00000001u;  // (i0 1 > i1 0: empty)
+    const uint32_t rc = g < n ? rects[((size_t)r * 6 + f) * n + g] : 0x00000001u;  // (i0 1 > i1 0: empty)
     const int i0 = (int)(rc & 0xffu), i1 = (int)((rc >> 8) & 0xffu), j0 = (int)((rc >> 16) & 0xffu), j1 = (int)(rc >> 24);
     const bool rows = !(j < j0 || j > j1 || i0 > i1);
     CellGeo G;
     uint32_t ty = 0u;
     if (rows) {
-      G = geo[(size_t)t * n + g];
+      G = geo[(size_t)r * n + g];
       ty = G.code >> 28;  // one list per collider type
     }
     __syncthreads();
@@ -291,7 +305,7 @@ __global__ __launch_bounds__(256) void cells_row_kernel(CellGeo* __restrict__ ge
       }
     }
     __syncthreads();
-    const size_t rbase = ((size_t)t * kCells + (size_t)(f * kCellG + j) * kCellG) * 3;  // the row's counters
+    const size_t rbase = (size_t)t * kCellStride + (size_t)(f * kCellG + j) * kCellG * 3;  // the row's counters
     if (!FILL) {
       if (tid < kCellG * 3 && s_cnt[tid]) atomicAdd(cb.count + rbase + tid, s_cnt[tid]);
     } else {
@@ -334,12 +348,17 @@ __device__ __forceinline__ void cells_scatter(const CellBufs& cb, uint32_t from,
   else cb.ent_s[to] = cb.ent[from];
 }
 template <bool COMPACT>
-__global__ __launch_bounds__(256) void cells_sort_kernel(CellBufs cb, int cells) {
+__global__ __launch_bounds__(256) void cells_sort_kernel(CellBufs cb, const int* __restrict__ sel, int cells) {
   constexpr int kR = kCellSortReg / 64;
   const int lane = threadIdx.x & 63;
-  const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-  if (i >= cells) return;  // (wave-uniform)
-  const uint32_t b = cb.start[i], e = cb.start[i + 1], n = e - b;
+  const int ri = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);  // list ri of the K targets' blocks, by rank
+  if (ri >= cells) return;  // (wave-uniform)
+  const int r = ri / kCellStride, wi = ri - r * kCellStride;
+  // a pad entry is no list: its next start may belong to another target's block, whose entries
+  // lie elsewhere in the arena once a target has been rebuilt on its own
+  if (wi >= kCells * 3) return;  // (wave-uniform)
+  const size_t i = (size_t)sel_target(sel, r) * kCellStride + (size_t)wi;
+  const uint32_t b = cb.start[i], e = cb.start[i + 1], n = e - b;  // (i + 1: at most the block's first pad entry)
   if (n <= 1u) {
     if (n == 1u && lane == 0) cells_scatter<COMPACT>(cb, b, b);
     return;
@@ -394,51 +413,72 @@ __global__ __launch_bounds__(256) void cells_sort_kernel(CellBufs cb, int cells)
 
 // The list starts (round 4: a per-target total kernel, a drop kernel and hipCUB's two-launch scan;
 // a one-workgroup version of all three measured 72 us, its waves walking their groups serially):
-//   cells_block_sum_kernel   one workgroup per 256 counters (a block lies in one target: kCells * 3
+//   cells_block_sum_kernel   one workgroup per 256 counters (a block lies in one target: kCellStride
 //                            is a multiple of 256): the block's sum, and one 64-bit atomic into its
 //                            target's entry total;
-//   cells_block_scan_kernel  one workgroup: the capacity check in target order (a target keeps its
-//                            lists while the running total fits the capacity, else ok = 0 and its
-//                            muffle rays test every collider), then the exclusive scan of the block
-//                            sums with a dropped target's blocks taken as 0 (its lists stay empty; the
-//                            fill pass skips it);
+//   cells_block_scan_kernel  one workgroup: the capacity check in rank order, starting from the
+//                            arena's tail (0 in a full build): a target keeps its lists while the
+//                            running total fits the capacity, else ok = 0 and its muffle rays test
+//                            every collider; then the exclusive scan of the block sums from that tail
+//                            with a dropped target's blocks taken as 0 (its lists stay empty; the
+//                            fill pass skips it); the new tail and the dropped count go to cb.tail and
+//                            to the pinned status word;
 //   cells_start_kernel       one workgroup per block: its starts, the block's offset plus the
 //                            exclusive scan of its counts.
-// The block sums and offsets sit in the cursor array, the targets' totals in `tot` (T x u64).
-__global__ __launch_bounds__(256) void cells_block_sum_kernel(CellBufs cb, unsigned long long* __restrict__ tot) {
-  static_assert((kCells * 3) % 256 == 0, "a block lies in one target");
+// The block sums and offsets sit in the cursor array (at the block's own index, target * kCellPerT +
+// block in target), the targets' totals in `tot` (T x u64).
+constexpr uint32_t kCellPerT = kCellStride / 256;  // blocks per target
+__global__ __launch_bounds__(256) void cells_block_sum_kernel(CellBufs cb, const int* __restrict__ sel,
+                                                              unsigned long long* __restrict__ tot) {
+  static_assert(kCellStride % 256 == 0 && (kCells * 3) % 256 == 0, "a block lies in one target");
   __shared__ uint32_t s[4];
-  uint32_t v = cb.count[(size_t)blockIdx.x * 256 + threadIdx.x];
+  const uint32_t r = blockIdx.x / kCellPerT;
+  const size_t gb = (size_t)sel_target(sel, (int)r) * kCellPerT + (blockIdx.x - r * kCellPerT);  // the block's own index
+  uint32_t v = cb.count[gb * 256 + threadIdx.x];
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
     const uint32_t sum = s[0] + s[1] + s[2] + s[3];
-    cb.cursor[blockIdx.x] = sum;
-    if (sum) atomicAdd(tot + blockIdx.x / ((kCells * 3) / 256), (unsigned long long)sum);
+    cb.cursor[gb] = sum;
+    if (sum) atomicAdd(tot + gb / kCellPerT, (unsigned long long)sum);
   }
 }
-__global__ __launch_bounds__(1024) void cells_block_scan_kernel(CellBufs cb, int T, uint32_t blocks,
-                                                                unsigned long long* __restrict__ tot) {
+// (T: the scene's targets; K, blocks = K * kCellPerT: those of this build)
+__global__ __launch_bounds__(1024) void cells_block_scan_kernel(CellBufs cb, const int* __restrict__ sel, int K, int T,
+                                                                uint32_t blocks, unsigned long long* __restrict__ tot) {
   __shared__ uint32_t s_keep[kMaxTargets];
   __shared__ uint32_t s_w[16];
-  constexpr uint32_t kPerT = (kCells * 3) / 256;  // blocks per target
+  __shared__ uint32_t s_base;
+  constexpr uint32_t kPerT = kCellPerT;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (tid == 0) {
-    unsigned long long run = 0ull;
-    for (int t = 0; t < T; ++t) {
+    const uint32_t base = sel ? min(cb.tail[0], cb.cap) : 0u;  // a partial build appends at the tail
+    unsigned long long run = base;
+    for (int r = 0; r < K; ++r) {
+      const int t = sel_target(sel, r);
       const unsigned long long c = tot[t];
       const bool keep = cb.ok[t] && run + c <= (unsigned long long)cb.cap;
       if (keep) run += c;
       else cb.ok[t] = 0u;
-      s_keep[t] = keep ? 1u : 0u;
+      s_keep[r] = keep ? 1u : 0u;
+    }
+    uint32_t dropped = 0u;  // targets with a finite bound and no lists: theirs did not fit
+    for (int t = 0; t < T; ++t) dropped += (!cb.ok[t] && isfinite(cb.far[t])) ? 1u : 0u;
+    s_base = base;
+    cb.tail[0] = (uint32_t)run;
+    cb.tail[1] = dropped;
+    if (cb.status) {
+      cb.status[0] = (uint32_t)run;
+      cb.status[1] = dropped;
     }
   }
   __syncthreads();
-  // thread i scans blocks [i * per, (i + 1) * per) (the kept total is at most cap < 2^32)
+  // thread i scans blocks [i * per, (i + 1) * per) by rank (the kept total is at most cap < 2^32)
+  auto own = [&](uint32_t b) { return (size_t)sel_target(sel, (int)(b / kPerT)) * kPerT + b % kPerT; };
   const uint32_t per = (blocks + 1023u) / 1024u, b0 = min(blocks, (uint32_t)tid * per), b1 = min(blocks, b0 + per);
   uint32_t sum = 0u;
-  for (uint32_t b = b0; b < b1; ++b) sum += s_keep[b / kPerT] ? cb.cursor[b] : 0u;
+  for (uint32_t b = b0; b < b1; ++b) sum += s_keep[b / kPerT] ? cb.cursor[own(b)] : 0u;
   uint32_t inc = sum;
   for (int o = 1; o < 64; o <<= 1) {
     const uint32_t u = __shfl_up(inc, o, 64);
@@ -446,21 +486,27 @@ __global__ __launch_bounds__(1024) void cells_block_scan_kernel(CellBufs cb, int
   }
   if (lane == 63) s_w[w] = inc;
   __syncthreads();
-  uint32_t run = inc - sum;
+  uint32_t run = s_base + inc - sum;
   for (int k = 0; k < w; ++k) run += s_w[k];
   for (uint32_t b = b0; b < b1; ++b) {
-    const uint32_t v = s_keep[b / kPerT] ? cb.cursor[b] : 0u;
-    cb.cursor[b] = run;  // the block's offset
+    const size_t gb = own(b);
+    const uint32_t v = s_keep[b / kPerT] ? cb.cursor[gb] : 0u;
+    cb.cursor[gb] = run;  // the block's offset
     run += v;
   }
-  if (b1 == blocks && b0 < b1) cb.start[(size_t)blocks * 256] = run;  // the sentinel: every kept entry
-  if (blocks == 0 && tid == 0) cb.start[0] = 0u;
+  if (!sel) {  // a full build: the sentinel after the last target's block (every kept entry)
+    if (b1 == blocks && b0 < b1) cb.start[(size_t)blocks * 256] = run;
+    if (blocks == 0 && tid == 0) cb.start[0] = 0u;
+  }
 }
-__global__ __launch_bounds__(256) void cells_start_kernel(CellBufs cb) {
+__global__ __launch_bounds__(256) void cells_start_kernel(CellBufs cb, const int* __restrict__ sel) {
   __shared__ uint32_t s[4];
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t r = blockIdx.x / kCellPerT;
+  const int t = sel_target(sel, (int)r);
+  const size_t gb = (size_t)t * kCellPerT + (blockIdx.x - r * kCellPerT);
+  const size_t i = gb * 256u + threadIdx.x;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint32_t v = cb.ok[blockIdx.x / ((kCells * 3) / 256)] ? cb.count[i] : 0u;
+  const uint32_t v = cb.ok[t] ? cb.count[i] : 0u;
   uint32_t inc = v;
   for (int o = 1; o < 64; o <<= 1) {
     const uint32_t u = __shfl_up(inc, o, 64);
@@ -468,16 +514,19 @@ __global__ __launch_bounds__(256) void cells_start_kernel(CellBufs cb) {
   }
   if (lane == 63) s[w] = inc;
   __syncthreads();
-  uint32_t base = cb.cursor[blockIdx.x];
+  uint32_t base = cb.cursor[gb];
   for (int k = 0; k < w; ++k) base += s[k];
   cb.start[i] = base + inc - v;
 }
 
 // Entry capacity: 128 cells per (target, collider) on average (a collider near its target spans
 // hundreds, a far one a few); a target whose lists do not fit falls back to testing every collider.
-size_t cells_entry_cap(int T, int C) {
+// A scene whose targets move on their own (relocations: launch_build_cells_targets appends a moved
+// target's lists at the arena's tail) gets four times that, the room for the garbage between two
+// compactions.
+size_t cells_entry_cap(int T, int C, bool relocations) {
   if (!cells_enabled(T, C)) return 0;
-  const size_t want = (size_t)128 * (size_t)T * (size_t)(C > 0 ? C : 1);
+  const size_t want = (size_t)(relocations ? 512 : 128) * (size_t)T * (size_t)(C > 0 ? C : 1);
   return std::min<size_t>(std::min<size_t>(std::max<size_t>(want, (size_t)1 << 16), (size_t)1 << 26),
                           (size_t)env_ll("ART_CELLS_CAP", 1ll << 26));
 }
@@ -492,14 +541,47 @@ bool cells_enabled(int T, int C) {
 // grid of a grid-stride launch over `items` work-items (at most 2^16 workgroups of 256)
 static unsigned stride_grid(long long items) { return (unsigned)std::max(1ll, std::min((items + 255) / 256, 1ll << 16)); }
 
-// workgroups of a row pass: one per (target, face, row, 256 colliders), at most 2^16 (grid-stride)
-static unsigned row_grid(int T, int n) {
-  return (unsigned)std::max(1ll, std::min((long long)T * 6 * kCellG * ((n + 255) >> 8), 1ll << 16));
+// workgroups of a row pass: one per (rank, face, row, 256 colliders), at most 2^16 (grid-stride)
+static unsigned row_grid(int K, int n) {
+  return (unsigned)std::max(1ll, std::min((long long)K * 6 * kCellG * ((n + 255) >> 8), 1ll << 16));
+}
+
+// The passes over K targets: all of them (sel nullptr, K = T: the arena is filled from 0) or the
+// selected ones (appended at the arena's tail).
+static void build_passes(const DevScene& sc, const CellBufs& cb, const int* sel, int K, hipStream_t st) {
+  const int T = sc.T, n = sc.ns + sc.na + sc.no;
+  const int cells = K * kCellStride;  // lists: (rank, cell, collider type), with the pads
+  const long long pairs = (long long)n * K;
+  CellGeo* geo = reinterpret_cast<CellGeo*>(cb.geo);
+  hipLaunchKernelGGL(cells_box_kernel, dim3(1), dim3(1024), 0, st, sc.cull, n, cb.box);
+  hipLaunchKernelGGL(cells_geo_kernel, dim3(stride_grid(std::max(pairs, (long long)cells + 1))), dim3(256), 0, st, sc, cb, sel, K,
+                     geo);
+  if (pairs > 0) {
+    hipLaunchKernelGGL(cells_row_kernel<false>, dim3(row_grid(K, n)), dim3(256), 0, st, geo, sel, K, cb, n);
+  }
+  // per-target totals, the capacity check and the list starts (three launches)
+  {
+    const uint32_t blocks = (uint32_t)cells / 256u;
+    unsigned long long* tot = cb.tcount;  // (zeroed by cells_geo_kernel)
+    if (blocks) hipLaunchKernelGGL(cells_block_sum_kernel, dim3(blocks), dim3(256), 0, st, cb, sel, tot);
+    hipLaunchKernelGGL(cells_block_scan_kernel, dim3(1), dim3(1024), 0, st, cb, sel, K, T, blocks, tot);
+    if (blocks) hipLaunchKernelGGL(cells_start_kernel, dim3(blocks), dim3(256), 0, st, cb, sel);
+  }
+  if (pairs > 0)
+    hipLaunchKernelGGL(cells_row_kernel<true>, dim3(row_grid(K, n)), dim3(256), 0, st, geo, sel, K, cb, n);
+  // each cell's entries by ascending near bound: muffle_kernel stops at the first one past its
+  // segment (every start is <= cap after the drop pass)
+  if (cells > 0) {
+    if (cb.compact)
+      hipLaunchKernelGGL(cells_sort_kernel<true>, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, cb, sel, cells);
+    else
+      hipLaunchKernelGGL(cells_sort_kernel<false>, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, cb, sel, cells);
+  }
 }
 
 int launch_build_cells(DevScene& sc, const CellBufs& cb, hipStream_t st) {
   const int T = sc.T, n = sc.ns + sc.na + sc.no;
-  const int cells = T * kCells * 3;  // lists: (target, cell, collider type)
+  const int cells = T * kCellStride;
   sc.cell_start = cb.start;
   sc.cell_ent = cb.ent_s;
   sc.cell_ent32 = reinterpret_cast<const uint32_t*>(cb.ent_s);
@@ -509,51 +591,57 @@ int launch_build_cells(DevScene& sc, const CellBufs& cb, hipStream_t st) {
   sc.cell_cap = cb.cap;
   if (cb.cap == 0) {  // no lists for this scene size (cells_enabled): every target tests every collider
     if (T > 0 && hipMemsetAsync(cb.ok, 0, (size_t)T * sizeof(uint32_t), st) != hipSuccess) return -1;
+    if (hipMemsetAsync(cb.tail, 0, 2 * sizeof(uint32_t), st) != hipSuccess) return -1;
     return 0;
   }
-  const long long pairs = (long long)n * T;
-  CellGeo* geo = reinterpret_cast<CellGeo*>(cb.geo);
-  hipLaunchKernelGGL(cells_box_kernel, dim3(1), dim3(1024), 0, st, sc.cull, n, cb.box);
-  hipLaunchKernelGGL(cells_geo_kernel, dim3(stride_grid(std::max(pairs, (long long)cells + 1))), dim3(256), 0, st, sc, cb, T,
-                     geo, (uint32_t)cells + 1);
-  if (pairs > 0) {
-    hipLaunchKernelGGL(cells_row_kernel<false>, dim3(row_grid(T, n)), dim3(256), 0, st, geo, T, cb, n);
-  }
-  // per-target totals, the capacity check and the list starts (three launches)
-  {
-    const uint32_t blocks = (uint32_t)cells / 256u;
-    unsigned long long* tot = cb.tcount;  // (zeroed by cells_geo_kernel)
-    if (blocks) hipLaunchKernelGGL(cells_block_sum_kernel, dim3(blocks), dim3(256), 0, st, cb, tot);
-    hipLaunchKernelGGL(cells_block_scan_kernel, dim3(1), dim3(1024), 0, st, cb, T, blocks, tot);
-    if (blocks) hipLaunchKernelGGL(cells_start_kernel, dim3(blocks), dim3(256), 0, st, cb);
-  }
-  if (pairs > 0)
-    hipLaunchKernelGGL(cells_row_kernel<true>, dim3(row_grid(T, n)), dim3(256), 0, st, geo, T, cb, n);
-  // each cell's entries by ascending near bound: muffle_kernel stops at the first one past its
-  // segment (every start is <= cap after the drop pass)
-  if (cb.compact)
-    hipLaunchKernelGGL(cells_sort_kernel<true>, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, cb, cells);
-  else
-    hipLaunchKernelGGL(cells_sort_kernel<false>, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, st, cb, cells);
+  build_passes(sc, cb, nullptr, T, st);
   if (env_ll("ART_DEBUG_CELLS", 0)) {  // diagnostics: the built lists' size and length histogram (synchronizes)
+    const long long pairs = (long long)n * T;
     std::vector<uint32_t> hs((size_t)cells + 1);
     if (hipMemcpyAsync(hs.data(), cb.start, hs.size() * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
         hipStreamSynchronize(st) == hipSuccess) {
       unsigned long long hist[18] = {};  // lists of length 0, 1, 2-3, 4-7, ... (log2 buckets)
       uint32_t longest = 0;
       for (int i = 0; i < cells; ++i) {
+        if (i % kCellStride >= kCells * 3) continue;  // a pad entry
         const uint32_t len = hs[(size_t)i + 1] - hs[i];
         longest = std::max(longest, len);
         hist[len == 0 ? 0 : std::min(17, 32 - __builtin_clz(len))]++;
       }
       fprintf(stderr, "[cells] T %d colliders %d: %u entries (capacity %u, %.1f per pair), %d lists, longest %u; lengths", T,
-              n, hs[(size_t)cells], cb.cap, (double)hs[(size_t)cells] / std::max(1ll, pairs), cells, longest);
+              n, hs[(size_t)cells], cb.cap, (double)hs[(size_t)cells] / std::max(1ll, pairs), T * kCells * 3, longest);
       for (int b = 0; b < 18; ++b)
         if (hist[b]) fprintf(stderr, " [%u..%u]:%llu", b == 0 ? 0u : 1u << (b - 1), b == 0 ? 0u : (1u << b) - 1u, hist[b]);
       fprintf(stderr, "\n");
     }
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_build_cells_targets(DevScene& sc, const CellBufs& cb, const int* d_tsel, int K, hipStream_t st) {
+  if (cb.cap == 0 || K <= 0) return 0;  // no lists: every muffle ray tests every collider
+  if (K > sc.T || !d_tsel) return -1;
+  build_passes(sc, cb, d_tsel, K, st);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Moved targets of art_targets_sync: positions[idx[j]] = pos[j] (an index outside [0, T) is skipped),
+// and the indices copied to device memory (tsel: the selection the list passes read many times; the
+// image may be pinned host memory).
+__global__ __launch_bounds__(256) void targets_scatter_kernel(const int* __restrict__ idx, const float* __restrict__ pos, int K,
+                                                              float* __restrict__ targets, int T, int* __restrict__ tsel) {
+  const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (j >= K) return;
+  const int t = idx[j];
+  tsel[j] = t;
+  if (t < 0 || t >= T) return;
+  targets[3 * t] = pos[3 * j];
+  targets[3 * t + 1] = pos[3 * j + 1];
+  targets[3 * t + 2] = pos[3 * j + 2];
+}
+void launch_scatter_targets(const int* idx, const float* pos, int K, float* targets, int T, int* tsel, hipStream_t st) {
+  if (K <= 0) return;
+  hipLaunchKernelGGL(targets_scatter_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, idx, pos, K, targets, T, tsel);
 }
 
 size_t cells_geo_bytes(int T, int C) {  // the CellGeo records, then the packed face rectangles (cell_rects)

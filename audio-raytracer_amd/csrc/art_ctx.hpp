@@ -71,6 +71,7 @@ struct Frame {
   int ns = 0, na = 0, no = 0;
   uint32_t stages = 0;
   bool resident = false;               // colliders come from the resident store (art_colliders.h)
+  bool res_targets = false;            // target positions and T come from the last art_targets_sync
   FrameParams fp{};
   FanLayout L{};
   std::vector<int2> slot_batch;        // permeation: [TC] ray range of the last batch writing slot s
@@ -149,6 +150,9 @@ struct Device {
   DevBuf exec;  // executed-work counters (ART_CTX_COUNT_EXECUTED)
   DevBuf cones; // the cell cone table (art_cells.hip), uploaded once
   CellBufs cb{};  // muffle candidate list buffers of the current scene (upload_scene)
+  DevBuf tsel;    // the moved targets of the last art_targets_sync (the partial list build's selection)
+  HostBuf cell_status;  // pinned (tail, dropped) of the cell lists' entry arena, written by the device (CellBufs::status)
+  bool cells_partial = false;  // a target's lists were rebuilt on their own since the last full build: the arena holds garbage
   DevBuf pairs; // global visibility pairs of the split raytrace path
   DevBuf dsp;   // per-sample DSP batch (art_dsp_process): samples, offsets, frames, params, states
   StoreDev store;
@@ -201,6 +205,20 @@ struct ColliderStore {
   uint64_t upd_seq = 0;
 };
 
+// The resident target store of a context (art_colliders.h, second half): the NextBatch mirror of
+// AudioTargetPositions with dirty marks, and the positions of the last sync (the JobBatch snapshot
+// that resident-target frames read).
+struct TargetStore {
+  std::vector<float> pos;         // count * 3
+  int count = 0;
+  std::vector<uint8_t> dirty;     // per target
+  std::vector<int> dirty_list;
+  int synced = 0;
+  bool store_synced = false;
+  std::vector<float> snap;        // synced * 3: the positions at the last sync
+  art_target_sync_stats last_sync{};
+};
+
 }  // namespace art
 
 struct art_ctx {
@@ -221,6 +239,7 @@ struct art_ctx {
   bool has_counts = false;
   std::vector<uint64_t> nonowned;  // per type (s, a, o): sum over targets of non-owned colliders
   art::ColliderStore store;
+  art::TargetStore targets;
   // Host phases of the Unity-facing frame (ART_HOST_TIMES=1 in the environment at art_create:
   // steady_clock marks in art_schedule / art_complete, means printed by art_destroy to stderr).
   struct HostPhases {
@@ -255,7 +274,8 @@ int fail(art_ctx* c, int code, const char* fmt, ...) __attribute__((format(print
 // art_frame.cpp
 int validate_desc(art_ctx* c, const art_frame_desc* d);
 FanLayout make_layout(const art_frame_desc* d, uint32_t out_flags);
-void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts = nullptr);
+void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts = nullptr,
+                bool resident_targets = false);
 void pack_inputs(const art_frame_desc* d, const Frame& f, uint8_t* h);
 struct ConeTable {
   CellCone cone[kCells];

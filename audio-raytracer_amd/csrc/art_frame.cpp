@@ -139,7 +139,7 @@ const ConeTable& cone_table() {
 }
 
 // Frame scalars + batch tables (Audio/AudioRayTracer.cs:161, Jobs/*:63-64, :36-37).
-void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts) {
+void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts, bool resident_targets) {
   // the direction-coherent order of the last frame is kept while its directions stay the same
   // (they are set once at init, AudioRayTracer.cs:72-86): a 3-KB compare instead of the sort
   std::vector<int> last_order;
@@ -150,6 +150,7 @@ void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int
   f.R = d->ray_count; f.H = d->max_hits_per_ray; f.T = d->audio_target_count;
   f.TC = d->batch_slots; f.bs = d->batch_size; f.nb = (f.R + f.bs - 1) / f.bs;
   f.ns = d->sphere_count; f.na = d->aabb_count; f.no = d->obb_count;
+  f.res_targets = resident_targets;
   if (resident_counts) {
     f.resident = true;
     f.ns = resident_counts[0]; f.na = resident_counts[1]; f.no = resident_counts[2];
@@ -212,7 +213,7 @@ void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int
   f.off_reset = o; o = align_up(o + (size_t)f.TC, 16);
   f.off_order = o; o = align_up(o + (size_t)f.R * 4, 16);
   f.raw_bytes = o;
-  f.cells_cap = (uint32_t)cells_entry_cap(f.T, f.ns + f.na + f.no);
+  f.cells_cap = (uint32_t)cells_entry_cap(f.T, f.ns + f.na + f.no, f.res_targets);
   Carver sizes{0};
   carve_decoded(sizes, f);
   carve_sort(sizes, f);
@@ -255,7 +256,7 @@ SortBufs carve_sort(Carver& c, const Frame& f) {
 }
 
 CellBufs carve_cells(Carver& c, const Frame& f) {
-  const size_t cells = (size_t)f.T * kCells * 3;  // lists per (target, cell, collider type)
+  const size_t cells = (size_t)f.T * kCellStride;  // counters per (target, cell, collider type), with the pads
   CellBufs cb{};
   cb.cap = f.cells_cap;
   cb.count = c.take<uint32_t>((cells + 1) * 4);
@@ -267,6 +268,7 @@ CellBufs carve_cells(Carver& c, const Frame& f) {
   cb.ok = c.take<uint32_t>((size_t)f.T * 4);
   cb.tcount = c.take<unsigned long long>((size_t)f.T * 8);
   cb.box = c.take<CullRec>(sizeof(CullRec));
+  cb.tail = c.take<uint32_t>(2 * sizeof(uint32_t));
   cb.ent = c.take<uint2>((size_t)cb.cap * 8);
   cb.geo = c.take<void>(cells_geo_bytes(f.T, f.ns + f.na + f.no));
   return cb;

@@ -87,11 +87,11 @@ struct DevScene {
   // Muffle candidate lists (art_cells.hip): for target t and direction cell c (a
   // cube map of kCellG x kCellG cells per face around the target), the colliders not owned by t
   // whose widened bounding sphere meets cell c's cone; entries (order code, distance from the
-  // target to the sphere) at cell_ent[cell_start[(t * kCells + c) * 3 + type] ..), one list per
+  // target to the sphere) at cell_ent[cell_start[t * kCellStride + c * 3 + type] ..), one list per
   // collider type (Sphere, AABB, OBB: muffle_kernel walks them with type-uniform tests), each by
   // ascending near bound. A target whose bound or list
   // overflowed (cell_ok[t] == 0) is tested against every collider instead.
-  const uint32_t* cell_start;     // [T * kCells * 3 + 1]
+  const uint32_t* cell_start;     // [T * kCellStride + 1]
   const uint2* cell_ent;          // [cell_cap]: (code, near bits), each cell's entries by ascending near_key
   const uint32_t* cell_ent32;     // the same lists in 4-B entries (in-type index | near_key << 16), when
   uint32_t cell_compact;          //   cell_compact (every type's count < 2^16)
@@ -122,6 +122,12 @@ inline void set_colliders(DevScene& sc, const DecodedColliders& d, const int n[3
 __host__ __device__ inline float cell_slack(float r) { return ART_CELL_SLACK_REL * r + ART_CELL_SLACK_ABS; }
 constexpr int kCellG = 32;                   // cells per cube-face axis
 constexpr int kCells = 6 * kCellG * kCellG;  // cells per target
+// Each target's block of list counters / starts is self-contained: kCells * 3 lists, then a pad of
+// counters that stay zero, so the start after a target's last list (st[3] in muffle_blocked, the
+// next start in cells_sort_kernel) is its own end and a target's entries can move in the arena on
+// their own (launch_build_cells_targets). 256: a 256-counter block still lies in one target.
+constexpr int kCellPad = 256;
+constexpr int kCellStride = kCells * 3 + kCellPad;
 // Cell cone (host table, art_frame.cpp ConeTable): unit axis and cos / sin of the half-angle plus slack.
 struct alignas(16) CellCone {
   float ax, ay, az, cos_a;
@@ -187,9 +193,9 @@ __host__ __device__ inline uint32_t near_key(uint32_t near_bits) {
 struct CellBufs {
   const CellCone* cones;          // [kCells]
   float alpha_max;                // largest cone half-angle (with slack)
-  uint32_t* count;                // [T * kCells * 3 + 1] entries per (cell, collider type)
-  uint32_t* start;                // [T * kCells * 3 + 1] exclusive scan of count (DevScene::cell_start)
-  uint32_t* cursor;               // [T * kCells * 3 + 1] scratch: the 256-counter block sums, then their offsets
+  uint32_t* count;                // [T * kCellStride + 1] entries per (cell, collider type), pads 0
+  uint32_t* start;                // [T * kCellStride + 1] per target, the exclusive scan of count (DevScene::cell_start)
+  uint32_t* cursor;               // [T * kCellStride + 1] scratch: the 256-counter block sums, then their offsets
   uint2* ent;                     // [cap] in fill order
   uint2* ent_s;                   // [cap] each cell's entries by ascending near bound (DevScene::cell_ent)
   uint32_t compact;               // 4-B entries in the same storage (DevScene::cell_compact)
@@ -200,11 +206,23 @@ struct CellBufs {
   uint32_t cap;                   // entry capacity; 0: no lists (cells_enabled false), every muffle ray tests every collider
   void* geo;                      // [T * C] per-(target, collider) geometry (cells_geo_bytes)
   CullRec* box;                   // [1] the union of the colliders' bounds (cells_box_kernel: the BVH root's box)
+  // The entry arena: a full build fills [0, tail), a partial build (launch_build_cells_targets)
+  // appends the selected targets' lists at the tail and leaves their old regions as garbage.
+  uint32_t* tail;                 // [2] device: entries in use, targets dropped for capacity
+  uint32_t* status;               // [2] the same pair in pinned host memory as the device sees it (or
+                                  //     nullptr), written by the scan kernel and read by the host without waiting
 };
 size_t cells_geo_bytes(int T, int C);
 bool cells_enabled(int T, int C);
-size_t cells_entry_cap(int T, int C);
+size_t cells_entry_cap(int T, int C, bool relocations = false);
 int launch_build_cells(DevScene& sc, const CellBufs& cb, hipStream_t st);
+// The lists of the K targets d_tsel[0..K) (device array, distinct indices) alone, from the scene's
+// current targets and colliders, appended at the arena's tail; a target that does not fit is
+// dropped (cell_ok 0: its muffle rays test every collider). Nothing to do without lists (cap 0).
+int launch_build_cells_targets(DevScene& sc, const CellBufs& cb, const int* d_tsel, int K, hipStream_t st);
+// positions[idx[j]] = pos[j] and tsel[j] = idx[j] for j < K (float3 each; idx and pos may be
+// pinned host memory, tsel is device memory of at least K ints).
+void launch_scatter_targets(const int* idx, const float* pos, int K, float* targets, int T, int* tsel, hipStream_t st);
 
 // Per-fan output block (byte offsets inside one fan's record; fan f starts at f * stride).
 struct FanLayout {

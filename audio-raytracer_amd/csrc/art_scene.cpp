@@ -97,7 +97,8 @@ int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in) {
   if (!dv.raw.reserve(f.raw_bytes) || !dv.soa.reserve(f.soa_bytes)) return fail(c, ART_E_NOMEM, "device allocation failed");
   const int key[10] = {f.ns, f.na, f.no, f.T, f.R, f.TC, f.H, f.fp.vol_n, f.fp.muf_n, (int)f.raw_bytes};
   UploadCache& last = dv.last;
-  if (!f.resident && last.valid && last.raw_p == dv.raw.p && last.soa_p == dv.soa.p &&
+  // (resident frames skip the compare: a sync rewrites the bound scene's records or targets in place)
+  if (!f.resident && !f.res_targets && last.valid && last.raw_p == dv.raw.p && last.soa_p == dv.soa.p &&
       memcmp(last.key, key, sizeof key) == 0 && memcmp(last.raw.data(), h_in, f.raw_bytes) == 0) {
     dv.sc = last.sc;  // device records, sorted copies and BVH are those of these same inputs
     dv.bound = true;
@@ -128,6 +129,14 @@ int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in) {
     if (!dv.cones.reserve(sizeof(CellCone) * kCells)) return fail(c, ART_E_NOMEM, "device allocation failed");
     HIP_TRY(c, hipMemcpyAsync(dv.cones.p, cone_table().cone, sizeof(CellCone) * kCells, hipMemcpyHostToDevice, dv.stream));
   }
+  // the arena's (tail, dropped) as the next art_targets_sync reads it, without waiting (a stale
+  // value only delays or hastens a compaction: the device checks the capacity itself)
+  if (!dv.cell_status.p) {
+    if (!dv.cell_status.reserve(2 * sizeof(uint32_t))) return fail(c, ART_E_NOMEM, "pinned allocation failed");
+    memset(dv.cell_status.p, 0, 2 * sizeof(uint32_t));
+  }
+  void* status = nullptr;
+  HIP_TRY(c, hipHostGetDevicePointer(&status, dv.cell_status.p, 0));
   // The cell lists need only the decoded colliders and the targets (cells_box_kernel gives their
   // distance bound), the BVH only the colliders: with a rebuilt BVH the lists build on the side
   // stream beside it (its surface-area passes occupy a few CUs for ~70 us), joined before the frame.
@@ -145,8 +154,10 @@ int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in) {
     cb.cones = static_cast<const CellCone*>(dv.cones.p);
     cb.alpha_max = cone_table().alpha_max;
     cb.compact = (ART_CELLS_COMPACT && f.ns < (1 << 16) && f.na < (1 << 16) && f.no < (1 << 16)) ? 1u : 0u;  // 4-B entries
+    cb.status = static_cast<uint32_t*>(status);
     dv.cb = cb;
     if (launch_build_cells(sc, dv.cb, cells_st) != 0) rc = fail(c, ART_E_DEVICE, "muffle cell lists failed");
+    dv.cells_partial = false;
   }
   if (rc) {  // kernels may already be queued on the side stream: later work on dv.stream waits for them
     if (cells_st != dv.stream && hipEventRecord(dv.side.join, cells_st) == hipSuccess)
@@ -161,7 +172,7 @@ int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in) {
   if (f.resident) snapshot_cell_base(c);  // the store's synced records (clean unless edited since)
   else c->store.cell_base_ok = false;
   HIP_TRY(c, hipGetLastError());
-  if (!f.resident) {
+  if (!f.resident && !f.res_targets) {
     last.raw.assign(h_in, h_in + f.raw_bytes);
     memcpy(last.key, key, sizeof key);
     last.raw_p = dv.raw.p;

@@ -1,7 +1,9 @@
-// art_store.cpp — the resident collider store (include/art_colliders.h): the host mirror of the
-// caller's collider lists with dirty marks, and art_colliders_sync, which uploads the changed
-// records to every device as a plan (plan_sync) and four steps (stage_image, sync_device per
-// device, commit_sync).
+// art_store.cpp — the resident scene store (include/art_colliders.h): the host mirrors of the
+// caller's collider lists and target positions with dirty marks, and art_colliders_sync /
+// art_targets_sync, each of which uploads what changed to every device as a plan (plan_sync /
+// plan_target_sync) and four steps (stage_image, sync_device per device, commit_sync; the target
+// half's are stage_target_image, sync_device_targets, commit_target_sync). Both kinds of sync
+// share the ring of pinned update images and its epoch events.
 #include "art_ctx.hpp"
 
 using namespace art;
@@ -29,6 +31,29 @@ StoreViews store_views(const int cap[3], Carver& raw, Carver& soa) {
   return v;
 }
 
+// A sync's slot in the ring of pinned update images and the ring's epoch (0 / 1).
+// The update image goes to ring slot seq % kUpdRing. A new epoch reuses the ring: every sync of the
+// previous epoch has finished reading its slot once that epoch's event (recorded after its last
+// sync, on that sync's stream) has completed. Each sync's stream is ordered after the earlier
+// syncs' (a launch on a new stream waits on the old one, a context-stream sync on the launch
+// stream), so that one event covers the whole epoch.
+struct RingSlot { int slot, ep; };
+RingSlot take_ring_slot(ColliderStore& s) {
+  const uint64_t seq = s.upd_seq++;
+  return RingSlot{(int)(seq % ColliderStore::kUpdRing), (int)((seq / ColliderStore::kUpdRing) & 1u)};
+}
+// A sync that starts a new epoch first waits for the last one (before it writes its image).
+int wait_ring_epoch(art_ctx* c, const RingSlot& r) {
+  if (r.slot != 0) return ART_OK;
+  for (Device& dv : c->devs)
+    if (dv.store.epoch_pending[r.ep ^ 1]) {
+      HIP_TRY(c, hipSetDevice(dv.id));
+      HIP_TRY(c, hipEventSynchronize(dv.store.epoch[r.ep ^ 1]));
+      dv.store.epoch_pending[r.ep ^ 1] = false;
+    }
+  return ART_OK;
+}
+
 // What one art_colliders_sync does, decided on the host before any device is given work.
 struct SyncPlan {
   int n[3];                   // the lists' counts
@@ -39,7 +64,7 @@ struct SyncPlan {
   size_t off_idx[3], off_rec[3], bytes;
   int nd;                     // dirty records over the kinds
   bool cells_ok;              // every changed collider stayed within the muffle cell lists' slack
-  int slot, ep;               // the image's slot in the pinned ring and the ring's epoch (0 / 1)
+  RingSlot ring;              // the image's slot in the pinned ring
 };
 
 // No HIP call, but it does change host state: it grows the devices' capacities (x2) and marks them
@@ -90,30 +115,17 @@ SyncPlan plan_sync(art_ctx& c) {
         break;
       }
   }
-  // The update image goes to ring slot seq % kUpdRing. A new epoch reuses the ring: every sync of the
-  // previous epoch has finished reading its slot once that epoch's event (recorded after its last
-  // sync, on that sync's stream) has completed. Each sync's stream is ordered after the earlier
-  // syncs' (a launch on a new stream waits on the old one, a context-stream sync on the launch
-  // stream), so that one event covers the whole epoch.
-  const uint64_t seq = s.upd_seq++;
-  p.slot = (int)(seq % ColliderStore::kUpdRing);
-  p.ep = (int)((seq / ColliderStore::kUpdRing) & 1u);
+  p.ring = take_ring_slot(s);
   return p;
 }
 
 // The pinned update image of the plan, in its ring slot (a new epoch first waits for the last one).
 int stage_image(art_ctx* c, const SyncPlan& p) {
   ColliderStore& s = c->store;
-  if (p.slot == 0)
-    for (Device& dv : c->devs)
-      if (dv.store.epoch_pending[p.ep ^ 1]) {
-        HIP_TRY(c, hipSetDevice(dv.id));
-        HIP_TRY(c, hipEventSynchronize(dv.store.epoch[p.ep ^ 1]));
-        dv.store.epoch_pending[p.ep ^ 1] = false;
-      }
+  if (int rc = wait_ring_epoch(c, p.ring)) return rc;
   if (!p.bytes) return ART_OK;
-  if (!s.h_upd[p.slot].reserve(p.bytes)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
-  uint8_t* h = static_cast<uint8_t*>(s.h_upd[p.slot].p);
+  if (!s.h_upd[p.ring.slot].reserve(p.bytes)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
+  uint8_t* h = static_cast<uint8_t*>(s.h_upd[p.ring.slot].p);
   for (int k = 0; k < 3; ++k) {
     const size_t rs = kRecSize[k];
     for (size_t j = 0; j < p.lists[k].size(); ++j) {
@@ -146,7 +158,7 @@ ScatterArgs scatter_args(const SyncPlan& p, const void* image, const StoreViews&
 // sync_device (a failure fails the sync, as before), by the destructor on its error exits.
 struct EpochMark {
   StoreDev& s;
-  const SyncPlan& p;
+  const RingSlot& p;
   hipStream_t ss;
   bool done = false;
   int record(art_ctx* c) {
@@ -174,7 +186,7 @@ int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt) 
   raw = Carver{reinterpret_cast<uintptr_t>(s.raw.p)};
   soa = Carver{reinterpret_cast<uintptr_t>(s.soa.p)};
   const StoreViews v = store_views(s.cap, raw, soa);
-  void* h = c->store.h_upd[p.slot].p;
+  void* h = c->store.h_upd[p.ring.slot].p;
   // Device-path frames still read the records / BVH being rewritten. The sync runs on the stream of
   // the last such frame when its completion is not recorded yet (the stream is valid until this
   // call, art_device.h): stream order puts it after that frame and before the next launch on the
@@ -184,7 +196,7 @@ int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt) 
   if (ss == dv.stream)
     if (int rc = dv.fence.wait(c, dv.stream)) return rc;
   s.stream = ss;
-  EpochMark epoch{s, p, ss};
+  EpochMark epoch{s, p.ring, ss};
   // moved colliders of a bound resident scene: one launch scatters the records from the pinned image
   // and refits the BVH (launch_sync_refit), below
   const bool refit_follows = p.nd && dv.bound && c->fr.resident && !p.counts_changed;
@@ -229,6 +241,7 @@ int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt) 
   }
   if (!p.cells_ok) {
     if (launch_build_cells(dv.sc, dv.cb, ss) != 0) return fail(c, ART_E_DEVICE, "muffle cell lists failed");
+    dv.cells_partial = false;  // (the full build compacts the entry arena)
     cells_rebuilt = true;
   }
   if (dv.sorted.gen != ~0ull) dv.sorted.gen = c->store.sync_gen;
@@ -276,9 +289,214 @@ void commit_sync(art_ctx* c, const SyncPlan& p, bool cells_rebuilt) {
   s.last_sync.bytes_uploaded = p.nd ? p.bytes : 0;
 }
 
+// ------------------------------------------------------------------------------- target half
+
+// The entry arena of a bound scene's cell lists is compacted (every target's lists rebuilt from
+// entry 0) by the next target sync once a target has been dropped for capacity, or once the tail
+// has passed this fraction of the capacity while the arena holds garbage (a target was rebuilt on
+// its own since the last full build; without garbage a compaction gains nothing): 7/8, so that a
+// scene whose compact lists fill a fifth of the arena (configs 2-5: 14-33 of 128 entries per pair)
+// takes moves of about three times its target count between compactions.
+constexpr uint32_t kArenaCompactNum = 7, kArenaCompactDen = 8;
+// A sync that moves at least 3/4 of the targets runs the full build: measured at config 2 (T = 4,
+// DESIGN.md §3b-targets), a step that relocates 3 of 4 targets costs 0.30 ms against 0.246 ms for
+// the full build (the arena fills within a few steps), one that relocates 2 of 4 0.195 ms.
+constexpr int kFullBuildNum = 3;  // (of 4)
+
+// What one art_targets_sync does, decided on the host before any device is given work.
+struct TargetSyncPlan {
+  int n;                   // the list's count
+  bool count_changed;      // against the last sync (true for the first)
+  std::vector<int> moved;  // dirty positions still in the list, ascending
+  // update image: [idx][positions], 16-B aligned sections; only when some device's bound
+  // resident-target scene has to follow the moves (image), else no device is given work
+  bool image;
+  size_t off_idx, off_pos, bytes;
+  RingSlot ring;
+};
+
+TargetSyncPlan plan_target_sync(art_ctx& c) {
+  TargetStore& t = c.targets;
+  TargetSyncPlan p;
+  p.n = t.count;
+  p.count_changed = !t.store_synced || p.n != t.synced;
+  for (int i : t.dirty_list)
+    if (i < p.n && t.dirty[(size_t)i]) p.moved.push_back(i);
+  std::sort(p.moved.begin(), p.moved.end());
+  p.moved.erase(std::unique(p.moved.begin(), p.moved.end()), p.moved.end());
+  bool bound = false;
+  for (const Device& dv : c.devs) bound |= dv.bound;
+  p.image = !c.cpu && bound && c.fr.res_targets && !p.count_changed && !p.moved.empty();
+  p.off_idx = 0;
+  p.off_pos = align_up(p.moved.size() * 4, 16);
+  p.bytes = p.image ? align_up(p.off_pos + p.moved.size() * 12, 16) : 0;
+  p.ring = p.image ? take_ring_slot(c.store) : RingSlot{-1, 0};
+  return p;
+}
+
+int stage_target_image(art_ctx* c, const TargetSyncPlan& p) {
+  if (int rc = wait_ring_epoch(c, p.ring)) return rc;
+  HostBuf& hb = c->store.h_upd[p.ring.slot];
+  if (!hb.reserve(p.bytes)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
+  uint8_t* h = static_cast<uint8_t*>(hb.p);
+  for (size_t j = 0; j < p.moved.size(); ++j) {
+    const int i = p.moved[j];
+    memcpy(h + p.off_idx + j * 4, &i, 4);
+    memcpy(h + p.off_pos + j * 12, c->targets.pos.data() + (size_t)i * 3, 12);
+  }
+  return ART_OK;
+}
+
+// One device's share of a moved-targets sync, async on the stream it picks (as sync_device): one
+// launch scatters the positions from the pinned image into the bound scene's target array, then
+// the moved targets' cell lists are rebuilt on their own (or every target's: full).
+int sync_device_targets(art_ctx* c, Device& dv, const TargetSyncPlan& p, int& rebuilt, bool& full_rebuild) {
+  StoreDev& s = dv.store;
+  HIP_TRY(c, hipSetDevice(dv.id));
+  const hipStream_t ss = (dv.fence.pending && !dv.fence.recorded) ? dv.fence.stream : dv.stream;
+  if (ss == dv.stream)
+    if (int rc = dv.fence.wait(c, dv.stream)) return rc;
+  s.stream = ss;
+  EpochMark epoch{s, p.ring, ss};
+  if (!dv.bound) return epoch.record(c);
+  const int K = (int)p.moved.size();
+  if (dv.sc.T != p.n || K > kMaxTargets) return fail(c, ART_E_STATE, "art_targets_sync: the bound scene's targets are not the store's");
+  if (!dv.tsel.reserve((size_t)kMaxTargets * sizeof(int))) return fail(c, ART_E_NOMEM, "device allocation failed");
+  void* hd = nullptr;  // the pinned image as the device sees it
+  HIP_TRY(c, hipHostGetDevicePointer(&hd, c->store.h_upd[p.ring.slot].p, 0));
+  const uint8_t* u = static_cast<const uint8_t*>(hd);
+  launch_scatter_targets(reinterpret_cast<const int*>(u + p.off_idx), reinterpret_cast<const float*>(u + p.off_pos), K,
+                         const_cast<float*>(dv.sc.targets), dv.sc.T, static_cast<int*>(dv.tsel.p), ss);
+  HIP_TRY(c, hipGetLastError());
+  dv.last.valid = false;  // the device's targets no longer are those of the last host-API upload
+  if (dv.cb.cap > 0) {
+    // the arena as the device last reported it (not waited for: the device checks the capacity itself)
+    const volatile uint32_t* status = static_cast<const volatile uint32_t*>(dv.cell_status.p);
+    const uint32_t tail = status ? status[0] : 0u, dropped = status ? status[1] : 0u;
+    const bool full = dropped > 0u || (dv.cells_partial && tail > dv.cb.cap / kArenaCompactDen * kArenaCompactNum) ||
+                      4 * K >= kFullBuildNum * dv.sc.T;
+    const int rc = full ? launch_build_cells(dv.sc, dv.cb, ss)
+                        : launch_build_cells_targets(dv.sc, dv.cb, static_cast<const int*>(dv.tsel.p), K, ss);
+    if (rc != 0) return fail(c, ART_E_DEVICE, "muffle cell lists failed");
+    dv.cells_partial = !full;
+    if (full) full_rebuild = true;
+    else rebuilt = K;
+  }
+  if (!s.done) HIP_TRY(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+  if (ss == dv.stream) HIP_TRY(c, hipEventRecord(s.done, ss));  // launches on other streams wait for it
+  return epoch.record(c);
+}
+
+void commit_target_sync(art_ctx* c, const TargetSyncPlan& p, int rebuilt, bool full_rebuild) {
+  TargetStore& t = c->targets;
+  for (int i : t.dirty_list)
+    if ((size_t)i < t.dirty.size()) t.dirty[(size_t)i] = 0;
+  t.dirty_list.clear();
+  t.synced = p.n;
+  t.snap.assign(t.pos.begin(), t.pos.begin() + (size_t)p.n * 3);  // the JobBatch snapshot frames read
+  t.store_synced = true;
+  if (p.count_changed && c->fr.res_targets)
+    for (Device& dv : c->devs) dv.bound = false;  // T is in the frame layout: bind again
+  // a full rebuild used the colliders' synced records: they are the lists' base now
+  if (full_rebuild && c->fr.resident) snapshot_cell_base(c);
+  t.last_sync.dirty_targets = (int32_t)p.moved.size();
+  t.last_sync.count_changed = p.count_changed ? 1 : 0;
+  t.last_sync.lists_rebuilt = rebuilt;
+  t.last_sync.lists_full_rebuild = full_rebuild ? 1 : 0;
+  t.last_sync.bytes_uploaded = p.image ? p.moved.size() * 16 : 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+ART_API int art_target_add(art_ctx* c, const float pos[3], int32_t* out_id) {
+  if (!c) return ART_E_INVALID;
+  if (!pos) return fail(c, ART_E_INVALID, "art_target_add: position is NULL");
+  TargetStore& t = c->targets;
+  if (t.count >= 32767) return fail(c, ART_E_UNSUPPORTED, "more than 32767 audio targets (the reference's ids are shorts)");
+  t.pos.insert(t.pos.end(), pos, pos + 3);
+  t.dirty.push_back(1);
+  t.dirty_list.push_back(t.count);
+  if (out_id) *out_id = t.count;  // the index in the list (AudioTargetRT.cs:40-44)
+  t.count++;
+  return ART_OK;
+}
+
+ART_API int art_target_set(art_ctx* c, int32_t id, const float pos[3]) { return art_target_set_many(c, &id, pos, 1); }
+
+ART_API int art_target_set_many(art_ctx* c, const int32_t* ids, const float* positions, int32_t n) {
+  if (!c) return ART_E_INVALID;
+  if (n < 0 || (n > 0 && (!ids || !positions))) return fail(c, ART_E_INVALID, "art_target_set_many: bad arguments");
+  TargetStore& t = c->targets;
+  for (int32_t j = 0; j < n; ++j)  // validate first: all or nothing
+    if (ids[j] < 0 || ids[j] >= t.count)
+      return fail(c, ART_E_INVALID, "art_target_set_many: id %d out of range [0, %d)", ids[j], t.count);
+  for (int32_t j = 0; j < n; ++j) {
+    const int id = ids[j];
+    float* p = t.pos.data() + (size_t)id * 3;
+    if (memcmp(p, positions + (size_t)j * 3, 12) == 0) continue;  // the same 12 bytes: nothing moved
+    memcpy(p, positions + (size_t)j * 3, 12);
+    if (!t.dirty[(size_t)id]) { t.dirty[(size_t)id] = 1; t.dirty_list.push_back(id); }
+  }
+  return ART_OK;
+}
+
+ART_API int art_target_remove_swapback(art_ctx* c, int32_t id) {
+  if (!c) return ART_E_INVALID;
+  TargetStore& t = c->targets;
+  if (id < 0 || id >= t.count) return ART_OK;  // skipped, as art_collider_remove_swapback
+  const int last = t.count - 1;
+  if (id != last) {  // AudioTargetManager.cs:67-73
+    memcpy(t.pos.data() + (size_t)id * 3, t.pos.data() + (size_t)last * 3, 12);
+    if (!t.dirty[(size_t)id]) { t.dirty[(size_t)id] = 1; t.dirty_list.push_back(id); }
+  }
+  t.count = last;
+  t.pos.resize((size_t)last * 3);
+  t.dirty.resize((size_t)last);
+  return ART_OK;
+}
+
+ART_API int art_target_get(art_ctx* c, int32_t id, float pos[3]) {
+  if (!c) return ART_E_INVALID;
+  if (!pos) return fail(c, ART_E_INVALID, "art_target_get: position is NULL");
+  const TargetStore& t = c->targets;
+  if (id < 0 || id >= t.count) return fail(c, ART_E_INVALID, "art_target_get: id %d out of range [0, %d)", id, t.count);
+  memcpy(pos, t.pos.data() + (size_t)id * 3, 12);
+  return ART_OK;
+}
+
+ART_API int art_target_count(art_ctx* c) { return c ? c->targets.count : ART_E_INVALID; }
+
+ART_API int art_target_synced_count(art_ctx* c) { return c ? c->targets.synced : ART_E_INVALID; }
+
+ART_API int art_targets_clear(art_ctx* c) {
+  if (!c) return ART_E_INVALID;
+  TargetStore& t = c->targets;
+  t.pos.clear(); t.dirty.clear(); t.dirty_list.clear(); t.count = 0;
+  return ART_OK;
+}
+
+ART_API int art_targets_last_sync(art_ctx* c, art_target_sync_stats* out) {
+  if (!c || !out) return ART_E_INVALID;
+  *out = c->targets.last_sync;
+  return ART_OK;
+}
+
+ART_API int art_targets_sync(art_ctx* c) {
+  if (!c) return ART_E_INVALID;
+  if (c->inflight) return fail(c, ART_E_STATE, "art_targets_sync: a frame is in flight (sync after art_complete)");
+  const TargetSyncPlan p = plan_target_sync(*c);
+  int rebuilt = 0;
+  bool full_rebuild = false;
+  if (p.image) {
+    if (int rc = stage_target_image(c, p)) return rc;
+    for (Device& dv : c->devs)
+      if (int rc = sync_device_targets(c, dv, p, rebuilt, full_rebuild)) return rc;
+  }
+  commit_target_sync(c, p, rebuilt, full_rebuild);
+  return ART_OK;
+}
 
 ART_API int art_collider_add(art_ctx* c, int32_t kind, const void* rec, int32_t* out_id) {
   if (!c) return ART_E_INVALID;

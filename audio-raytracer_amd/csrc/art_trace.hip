@@ -1533,7 +1533,8 @@ __device__ __forceinline__ bool muffle_blocked(const DevScene& sc, vec3 off, vec
   if (lists) {
     // the cell's Sphere, AABB and OBB lists in turn (a type-uniform test per loop), each by
     // ascending near bound: a walk stops at the first entry past the segment
-    const uint32_t* st = sc.cell_start + ((size_t)t * kCells + cube_cell(v)) * 3;
+    // (st[3] of the target's last cell is its block's first pad start: the target's own end)
+    const uint32_t* st = sc.cell_start + (size_t)t * kCellStride + (size_t)cube_cell(v) * 3;
     const float lim = maxd * 1.00001f + 1e-6f;
     const uint32_t klim = near_key(__float_as_uint(lim));
     const uint4 se = make_uint4(st[0], st[1], st[2], st[3]);

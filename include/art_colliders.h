@@ -1,6 +1,7 @@
 /*
- * art_colliders.h — device-resident collider store (SURVEY.md §8 f rank 2, the collider upload
- * path on the near side of the ray tracer).
+ * art_colliders.h — the device-resident scene store, both halves: the collider lists (SURVEY.md
+ * §8 f rank 2, the collider upload path on the near side of the ray tracer) and the audio-target
+ * positions (the second half of this file).
  *
  * Reference (paths relative to "Assets/C# Scripts/"):
  *   NativeJobBatch<T>                       DataTypes/NativeJobBatch.cs:8-56
@@ -27,6 +28,20 @@
  * Baking a collider struct from its transform (GetBakedColliderStruct, AudioOBBCollider.cs:31-66)
  * stays with the caller: it uses the engine's transform and quaternion math, and its result (the
  * 20/26/16-byte struct) is the contract.
+ *
+ * The target half mirrors AudioTargetManager over NativeJobBatch<float3>:
+ *   AudioTargetManager.AddAudioTargetToSystem      Audio/AudioTargetManager.cs:49-57 (the position is
+ *                                                  appended, AudioTarget/AudioTargetRT.cs:40-44)
+ *   AudioTargetManager.RemoveAudioTargetFromSystem :59-96 (the last position moves into the hole, :73, :95)
+ *   AudioTargetManager.UpdateColiderInSystem       :97-100 -> AudioTargetRT.UpdateToAudioSystem
+ *                                                  (AudioTarget/AudioTargetRT.cs:45-48), called for a target
+ *                                                  that is not static and moved (:8-10, :53-62)
+ *   AudioTargetManager.UpdateJobBatch              :105-110 (once per frame)
+ * The context keeps the NextBatch mirror of the positions with dirty marks. art_targets_sync is
+ * UpdateJobBatch: K moved targets cost an upload of K positions and, on a bound device scene, the
+ * rebuild of those K targets' muffle cell lists; the BVH, the other targets' lists and the frame
+ * layout stay. With ART_CTX_RESIDENT_TARGETS set, art_schedule and art_scene_bind take the
+ * positions and the target count from the last target sync.
  */
 #ifndef ART_COLLIDERS_H
 #define ART_COLLIDERS_H
@@ -85,6 +100,65 @@ typedef struct {
 } art_collider_sync_stats;
 
 ART_API int art_colliders_last_sync(art_ctx* ctx, art_collider_sync_stats* out);
+
+/* ------------------------------------------------------------------ audio targets (ABI 3.4) */
+
+/* art_set_flags bit: frames read the resident target positions (desc.audio_target_positions must
+ * be NULL and desc.audio_target_count 0). Combines freely with ART_CTX_RESIDENT_COLLIDERS.
+ * art_fan_layout_get takes no context: pass it a copy of the desc with audio_target_count set to
+ * art_target_synced_count (its positions pointer any non-NULL value; it is not read). */
+#define ART_CTX_RESIDENT_TARGETS 0x800u
+
+/* AddAudioTargetToSystem (:49-57): appends pos; *out_id = its index in the list. */
+ART_API int art_target_add(art_ctx* ctx, const float pos[3], int32_t* out_id);
+
+/* UpdateToAudioSystem (AudioTargetRT.cs:45-48): positions[id] = pos. ART_E_INVALID if id is out of
+ * range. A set to the same 12 bytes marks nothing dirty. */
+ART_API int art_target_set(art_ctx* ctx, int32_t id, const float pos[3]);
+
+/* n updates in one call (ids[j] <- positions[3j..3j+2]); all ids are checked before anything
+ * changes. */
+ART_API int art_target_set_many(art_ctx* ctx, const int32_t* ids, const float* positions, int32_t n);
+
+/* RemoveAudioTargetFromSystem (:59-96): the last position moves to id. An id out of range is
+ * skipped (returns ART_OK, nothing changes), as art_collider_remove_swapback does. The colliders
+ * owned by the swapped target keep their audio_target_id: re-numbering them (the reference's id
+ * pool, :75-86, and the colliders' own updates) stays with the caller, through art_collider_set. */
+ART_API int art_target_remove_swapback(art_ctx* ctx, int32_t id);
+
+/* positions[id] of the mirror (NextBatch, including unsynced changes). */
+ART_API int art_target_get(art_ctx* ctx, int32_t id, float pos[3]);
+
+/* NextBatch.Length (>= 0), or a negative error code. */
+ART_API int art_target_count(art_ctx* ctx);
+
+/* The target count of the last art_targets_sync (what resident-target frames use), or a negative
+ * error code. */
+ART_API int art_target_synced_count(art_ctx* ctx);
+
+/* Drop every target (the next sync publishes the empty list). */
+ART_API int art_targets_clear(art_ctx* ctx);
+
+/* UpdateJobBatch (:105-110): publish the mirror to every device of the context. Stream-ordered
+ * exactly like art_colliders_sync (the same stream choice and fences). ART_E_STATE while a frame is
+ * in flight. A count change (add, remove, clear) unbinds a bound resident-target scene: T is part
+ * of the frame layout, so the next art_scene_bind / art_schedule builds everything again. */
+ART_API int art_targets_sync(art_ctx* ctx);
+
+/* What the last art_targets_sync moved. */
+typedef struct {
+    int32_t dirty_targets;      /* positions that changed since the last sync and are still in the list */
+    int32_t count_changed;      /* 1 if the list's length changed (the first sync included) */
+    int32_t lists_rebuilt;      /* targets whose muffle cell lists were rebuilt on their own */
+    int32_t lists_full_rebuild; /* 1 if every target's lists were rebuilt (the entry arena compacted) */
+    uint64_t bytes_uploaded;    /* H2D bytes of the sync (indices + positions) */
+} art_target_sync_stats;
+
+ART_API int art_targets_last_sync(art_ctx* ctx, art_target_sync_stats* out);
+
+/* Diagnostics (synchronizes device 0): entries in use and capacity of the bound scene's muffle
+ * cell-list arena, and the targets currently without lists because theirs did not fit. */
+ART_API int art_debug_cells_arena(art_ctx* ctx, uint64_t* used, uint64_t* cap, uint32_t* dropped_targets);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,12 @@
 """bench.py's dynamic step alone (1 % of the colliders moved per step: art_collider_set_many +
 art_colliders_sync + art_launch_device on torch's stream), for its kernel / copy timeline under
 rocprofv3 --kernel-trace --memory-copy-trace, and its ms per step. GPU box only.
-    python3 tools/dynamic_run.py [config] [steps]"""
+    python3 tools/dynamic_run.py [config] [steps]
+The moving-target step, timed the same way:
+    python3 tools/dynamic_run.py [config] [steps] --targets K            K of the T targets moved per step:
+                                 art_target_set_many + art_targets_sync + art_launch_device
+    python3 tools/dynamic_run.py [config] [steps] --targets K --rebind   the same step without the target
+                                 store: art_scene_bind with the new positions + art_launch_device"""
 import os
 import sys
 import time
@@ -19,9 +24,79 @@ from art.colliders import ColliderStore, resident_frame  # noqa: E402
 from bench import jitter_records  # noqa: E402
 
 
+def timed(one, steps, what, cfg):
+    for i in range(10):
+        one(i)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        one(i)
+    torch.cuda.synchronize()
+    print(f"config {cfg.index}: {what} {(time.perf_counter() - t0) / steps * 1e3:.4f} ms over {steps} steps", flush=True)
+
+
+def target_steps(cfg, steps, K, rebind):
+    """K of the T targets moved by up to 2 units per step, eight pre-made variants (a target's
+    position differs between the variants that move it, so every step's K sets are real moves)."""
+    scene, org, params = art.synth(cfg)
+    S, T = org.shape[0], scene.T
+    K = min(K, T)
+    rng = np.random.default_rng(7)
+    variants = []
+    for v in range(8):
+        ids = np.sort((v * K + np.arange(K)) % T).astype(np.int32)  # every target in turn: each step moves K
+        variants.append((ids, (scene.targets[ids] + rng.uniform(-2, 2, (K, 3))).astype(np.float32)))
+    ctx = art.Context(1)
+    out = art.FanOutputs(S, cfg.R, cfg.H, T, 1, dsp=params.dsp is not None)
+    frame = art.Frame(scene, params, org, out)
+    lay = art.fan_layout(frame)
+    d_org = torch.from_numpy(np.ascontiguousarray(org)).cuda()
+    d_blk = torch.zeros(S * lay["stride"], dtype=torch.uint8, device="cuda")
+    sp = torch.cuda.current_stream().cuda_stream
+    if rebind:
+        frames, pos = [], scene.targets.copy()
+        for ids, p in variants:  # each variant's whole scene, as a caller without the store binds it
+            pos = pos.copy()
+            pos[ids] = p
+            sc = art.Scene(dirs=scene.dirs, targets=pos, spheres=scene.spheres, aabbs=scene.aabbs, obbs=scene.obbs)
+            frames.append(art.Frame(sc, params, org, out))
+
+        def one(i):
+            ctx.bind(frames[i % len(frames)])
+            ctx.launch_device(d_org.data_ptr(), S, d_blk.data_ptr(), 0, sp)
+        timed(one, steps, f"{K} of {T} targets moved, art_scene_bind + launch", cfg)
+    else:
+        from art.targets import TargetStore, resident_targets_frame
+        store = TargetStore(ctx)
+        store.add_many(scene.targets)
+        store.sync()
+        ctx.set_flags(abi.ART_CTX_RESIDENT_TARGETS)
+        ctx.bind(resident_targets_frame(frame))
+        stats = {}
+
+        def one(i):
+            ids, p = variants[i % len(variants)]
+            store.set_many(ids, p)
+            st = store.sync()
+            stats[(st["lists_rebuilt"], st["lists_full_rebuild"])] = stats.get((st["lists_rebuilt"], st["lists_full_rebuild"]), 0) + 1
+            ctx.launch_device(d_org.data_ptr(), S, d_blk.data_ptr(), 0, sp)
+        timed(one, steps, f"{K} of {T} targets moved, art_target_set_many + art_targets_sync + launch", cfg)
+        print(f"  syncs by (lists_rebuilt, lists_full_rebuild): {stats}; arena {store.cells_arena()}", flush=True)
+    ctx.close()
+
+
 def main():
-    cfg = art.CONFIGS[int(sys.argv[1]) if len(sys.argv) > 1 else 2]
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 500
+    argv = sys.argv[1:]
+    K = None
+    if "--targets" in argv:
+        at = argv.index("--targets")
+        K = int(argv[at + 1])
+        del argv[at:at + 2]
+    args = [a for a in argv if not a.startswith("--")]
+    cfg = art.CONFIGS[int(args[0]) if len(args) > 0 else 2]
+    steps = int(args[1]) if len(args) > 1 else 500
+    if K is not None:
+        return target_steps(cfg, steps, K, "--rebind" in argv)
     scene, org, params = art.synth(cfg)
     S = org.shape[0]
     ctx = art.Context(1)
