@@ -191,6 +191,11 @@ class art_dsp_source_params(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class art_listener(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("rotation", C.c_float * 4)]
+
+
+LISTENER = np.dtype([("position", np.float32, 3), ("rotation", np.float32, 4)])
 DSP_STATE = np.dtype([("previous_muffle", np.float32, 2), ("previous_lp", np.float32, 2),
                       ("previous_hp", np.float32, 2), ("previous_input", np.float32, 2)])
 DSP_SOURCE_PARAMS = np.dtype([("muffle_alpha", np.float32), ("dry_boost", np.float32), ("gain_left", np.float32),
@@ -233,6 +238,11 @@ SIGNATURES = {
                                         C.POINTER(art_dsp_source_params)]),
     "art_dsp_process_device": (I32, [VP, VP, VP, VP, I32, I32, VP]),
     "art_fibonacci_directions_device": (I32, [VP, I32, VP, VP]),
+    "art_dsp_tick_params_host": (I32, [C.POINTER(art_spatializer_settings), I32, VP, C.POINTER(art_fan), I32, VP, I32, VP,
+                                       VP]),
+    "art_dsp_settings_bind": (I32, [VP, C.POINTER(art_spatializer_settings), I32]),
+    "art_dsp_tick_params_device": (I32, [VP, VP, U32, I32, VP, VP, VP, VP]),
+    "art_dsp_tick_device": (I32, [VP, VP, U32, I32, VP, VP, VP, VP, I32, VP, VP]),
     # art_colliders.h
     "art_collider_add": (I32, [VP, I32, VP, C.POINTER(I32)]),
     "art_collider_set": (I32, [VP, I32, I32, VP]),

@@ -4,6 +4,11 @@ Mirrors AudioSpatializer.OnAudioFilterRead (Audio/AudioTarget/AudioSpatializer.c
 AudioSource holds an interleaved stereo buffer processed in place and the filter state the C#
 MuffleDSP / BinauralDSP structs keep between calls. The product path runs on the GPU through
 libart.so; there is no CPU fallback.
+
+The audio tick (tick_params_host, bind_settings, tick_params_device, tick_device) is the main-thread
+link in front of it (AudioSpatializer.UpdateSpatializer / OnLateUpdate, AudioSpatializer.cs:55-67):
+the settings section of a frame's result blocks and each fan's listener become the per-buffer
+scalars, on the device and on the caller's stream, or on the host.
 """
 from __future__ import annotations
 
@@ -109,3 +114,86 @@ def source_params(settings: SpatializerSettings, source: AudioSource, sample_rat
     if rc:
         raise ValueError(f"art_dsp_source_params_get: {rc}")
     return out
+
+
+@dataclass
+class Listener:
+    """The AudioListener's transform: position and rotation (quaternion x, y, z, w)."""
+    position: tuple = (0.0, 0.0, 0.0)
+    rotation: tuple = (0.0, 0.0, 0.0, 1.0)
+
+
+def listeners_array(listeners) -> np.ndarray:
+    """Listener objects (or an abi.LISTENER array) as one abi.LISTENER array, one record per fan."""
+    if isinstance(listeners, np.ndarray):
+        assert listeners.dtype == abi.LISTENER
+        return np.ascontiguousarray(listeners)
+    out = np.zeros(len(listeners), abi.LISTENER)
+    for i, l in enumerate(listeners):
+        out[i]["position"] = l.position
+        out[i]["rotation"] = l.rotation
+    return out
+
+
+def tick_params_host(settings: SpatializerSettings, listeners, fan_settings: np.ndarray, target_positions: np.ndarray,
+                     volume: np.ndarray | None = None, sample_rate: int = 48000) -> np.ndarray:
+    """art_dsp_tick_params_host: the spatializer parameters of every (fan, target) source from the
+    fans' settings (abi.SETTINGS [fan_count, T], a frame's FanOutputs.settings), one listener per
+    fan and the scene's target positions; returns DSP_SOURCE_PARAMS [fan_count * T]."""
+    fs = np.ascontiguousarray(fan_settings)
+    assert fs.dtype == abi.SETTINGS and fs.ndim == 2
+    S, T = fs.shape
+    ls = listeners_array(listeners)
+    assert ls.size == S
+    tp = np.ascontiguousarray(target_positions, np.float32).reshape(-1, 3)
+    assert tp.shape[0] == T
+    fans = (abi.art_fan * max(S, 1))()
+    for i in range(S):
+        fans[i].settings = fs[i].ctypes.data
+    vol = None
+    if volume is not None:
+        vol = np.ascontiguousarray(volume, np.float32).reshape(-1)
+        assert vol.size == S * T
+    out = np.zeros(S * T, abi.DSP_SOURCE_PARAMS)
+    st = settings.to_c()
+    rc = abi.load_library().art_dsp_tick_params_host(C.byref(st), sample_rate, ls.ctypes.data, fans, S, tp.ctypes.data, T,
+                                                     vol.ctypes.data if vol is not None else None, out.ctypes.data)
+    if rc:
+        raise ValueError(f"art_dsp_tick_params_host: {abi.ERROR_NAMES.get(rc, rc)}")
+    return out
+
+
+def _dptr(x) -> int | None:
+    """A device buffer as the C ABI takes it: a torch tensor's data pointer, or a raw pointer / None."""
+    if x is None or isinstance(x, int):
+        return x
+    assert x.is_contiguous()
+    return x.data_ptr()
+
+
+def bind_settings(ctx, settings: SpatializerSettings, sample_rate: int = 48000):
+    """art_dsp_settings_bind: the spatializer settings of the later ticks (curves uploaded once)."""
+    st = settings.to_c()
+    rc = ctx.lib.art_dsp_settings_bind(ctx.ptr, C.byref(st), sample_rate)
+    if rc:
+        ctx._raise(rc)
+
+
+def tick_params_device(ctx, d_block, fan_count: int, d_listeners, d_params, d_volume=None, out_flags: int = 0,
+                       stream: int | None = None):
+    """art_dsp_tick_params_device on `stream` (not synchronised); buffers are torch tensors or raw
+    device pointers."""
+    rc = ctx.lib.art_dsp_tick_params_device(ctx.ptr, _dptr(d_block), out_flags, fan_count, _dptr(d_listeners),
+                                            _dptr(d_volume), _dptr(d_params), stream)
+    if rc:
+        ctx._raise(rc)
+
+
+def tick_device(ctx, d_block, fan_count: int, d_listeners, d_data, d_state, frames: int, d_params, d_volume=None,
+                out_flags: int = 0, stream: int | None = None):
+    """art_dsp_tick_device on `stream` (not synchronised): the parameter step, then the per-sample
+    chain over d_data (float [fan_count * T][frames][2]) and d_state."""
+    rc = ctx.lib.art_dsp_tick_device(ctx.ptr, _dptr(d_block), out_flags, fan_count, _dptr(d_listeners), _dptr(d_volume),
+                                     _dptr(d_data), _dptr(d_state), frames, _dptr(d_params), stream)
+    if rc:
+        ctx._raise(rc)

@@ -45,8 +45,9 @@ namespace {
 // ART_CTX_TIME_EACH_KERNEL.
 // 3.1: ART_CTX_EVENT_EACH_LAUNCH, art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*;
 // 3.3: art_debug_echo_decided; 3.4: the resident target store (art_target_*, art_targets_*,
-// ART_CTX_RESIDENT_TARGETS, art_debug_cells_arena)
-constexpr uint32_t kAbiVersion = (3u << 16) | 4u;
+// ART_CTX_RESIDENT_TARGETS, art_debug_cells_arena); 3.5: the audio tick (art_listener,
+// art_dsp_tick_params_host, art_dsp_settings_bind, art_dsp_tick_params_device, art_dsp_tick_device)
+constexpr uint32_t kAbiVersion = (3u << 16) | 5u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -242,7 +243,7 @@ ART_API void art_destroy(art_ctx* c) {
       dv.fence.pending = false;
     }
     dv.raw.release(); dv.soa.release(); dv.origins.release(); dv.block.release(); dv.acc.release(); dv.counts.release();
-    dv.exec.release(); dv.pairs.release(); dv.dsp.release(); dv.cones.release(); dv.tsel.release();
+    dv.exec.release(); dv.pairs.release(); dv.dsp.release(); dv.tick_curves.release(); dv.cones.release(); dv.tsel.release();
     dv.cell_status.release();
     dv.store.raw.release(); dv.store.soa.release(); dv.store.upd.release();
     if (dv.store.done) (void)hipEventDestroy(dv.store.done);
@@ -547,25 +548,12 @@ static int launch_common(art_ctx* c, const float* d_origins, int32_t fan_count, 
     f.L = make_layout(&tmp, out_flags);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);  // NULL is the HIP default stream (torch's default)
-  if ((f.resident || f.res_targets) && dv.store.done && st != dv.store.stream) HIP_TRY(c, hipStreamWaitEvent(st, dv.store.done, 0));
-  // frames share the context's accumulators and pair buffers: a launch on another stream than the
-  // previous one waits for it (on the same stream, stream order already does)
-  if (dv.fence.pending && st != dv.fence.stream) {
-    int rc = dv.fence.mark_done(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamWaitEvent(st, dv.fence.done, 0));
-  }
-  int rc = enqueue_kernels(c, dv, f, d_origins, fan_count, static_cast<uint8_t*>(d_block), st, count);
+  int rc = scene_reader_begin(c, dv, f, st);
   if (rc) return rc;
-  // the next sync, bind or schedule rewrites the scene or reuses the shared buffers on dv.stream:
-  // after this frame (LaunchFence::wait records the event on this stream then)
-  dv.fence.pending = true;
-  dv.fence.stream = st;
-  dv.fence.recorded = false;
-  if (c->flags & ART_CTX_EVENT_EACH_LAUNCH) {  // opt-in: the caller may drop its stream after this call
-    int rc2 = dv.fence.mark_done(c);
-    if (rc2) return rc2;
-  }
+  rc = enqueue_kernels(c, dv, f, d_origins, fan_count, static_cast<uint8_t*>(d_block), st, count);
+  if (rc) return rc;
+  rc = scene_reader_end(c, dv, st);
+  if (rc) return rc;
   if (count) return read_counts(c, dv, st, out, false);
   return ART_OK;
 }

@@ -155,6 +155,7 @@ struct Device {
   bool cells_partial = false;  // a target's lists were rebuilt on their own since the last full build: the arena holds garbage
   DevBuf pairs; // global visibility pairs of the split raytrace path
   DevBuf dsp;   // per-sample DSP batch (art_dsp_process): samples, offsets, frames, params, states
+  DevBuf tick_curves;  // the baked curves of the bound spatializer settings (art_dsp_settings_bind): muffle | reverb volume
   StoreDev store;
   LaunchFence fence;
   uint64_t exec_launches = 0;
@@ -228,6 +229,13 @@ struct art_ctx {
   uint32_t flags = 0;
   art::HostBuf h_in, h_block;
   art::HostBuf h_dsp;            // staging of art_dsp_process
+  // the audio tick's spatializer settings (art_dsp_settings_bind): the scalars, the curves pointing
+  // into devs[0].tick_curves
+  struct TickSettings {
+    bool bound = false;
+    art_spatializer_settings st{};
+    int sample_rate = 0;
+  } tick;
   art::Frame fr;                 // frame of the bound scene / last schedule
   // in-flight frame
   bool inflight = false;
@@ -292,6 +300,8 @@ CellBufs carve_cells(Carver& c, const Frame& f);
 
 // art_scene.cpp
 int ensure_side(art_ctx* c, SideStream& s);  // the stream and its fork / join events, created once
+int scene_reader_begin(art_ctx* c, Device& dv, const Frame& f, hipStream_t st);
+int scene_reader_end(art_ctx* c, Device& dv, hipStream_t st);
 int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in);
 void snapshot_cell_base(art_ctx* c);
 bool cell_still_valid(int kind, const uint8_t* now, const uint8_t* base);

@@ -7,7 +7,8 @@
 // on the pass's own filter state, so the passes fuse into one loop over samples with identical
 // results. The quantities the C# recomputes per sample (curve lookups, cutoffs, filter alphas)
 // are constant over a buffer and are computed once on the host with the same float operations
-// (art_dsp_source_params_get); the GPU runs the recurrences, one lane per source, both channels
+// (art_dsp_source_params_get), or on the device from a frame's result blocks (the audio tick,
+// dsp_tick_params_kernel; art_dsp_math.hpp holds the shared sequence); the GPU runs the recurrences, one lane per source, both channels
 // interleaved (two independent chains per lane).
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "../../include/art_dsp.h"
+#include "art_dsp_math.hpp"
 #include "art_internal.hpp"
 
 #pragma clang fp contract(off)
@@ -27,38 +29,6 @@ namespace art {
 namespace {
 
 constexpr int kDspBlock = 256;
-
-// Unity.Mathematics semantics (same definitions as unity_math.hpp, host side)
-inline float umin(float x, float y) { return (y != y || x < y) ? x : y; }
-inline float umax(float x, float y) { return (y != y || x > y) ? x : y; }
-inline float usaturate(float x) { return umax(0.0f, umin(1.0f, x)); }
-inline float ulerp(float a, float b, float s) { return a + s * (b - a); }
-inline float uclamp(float x, float a, float b) { return umax(a, umin(b, x)); }
-constexpr float kToDegrees = 57.29578f;      // math.degrees
-constexpr float kToRadians = 0.0174532924f;  // math.radians
-constexpr float kDoublePi = 2.0f * 3.14159265f;  // MuffleDSP.cs:35 / BinauralDSP.cs:84
-
-// NativeSampledAnimationCurve.Evaluate (NativeSampledAnimationCurve.cs:64-89)
-float curve_eval(const art_curve& c, float time) {
-  const float percent = time / c.length;
-  const int n = c.sample_count;
-  const float cp = umax(0.0f, umin((float)(n - 1), percent * (float)(n - 1)));
-  const int fi = (int)std::floor(cp), ci = (int)std::ceil(cp);
-  return ulerp(c.baked[fi], c.baked[ci], cp - (float)fi);
-}
-
-float lowpass_alpha(float cutoff, float sr) {  // MuffleDSP.cs:40-42, BinauralDSP.cs:89-91
-  const float rc = 1.0f / (cutoff * kDoublePi);
-  const float dt = 1.0f / sr;
-  return dt / (rc + dt);
-}
-float highpass_alpha(float cutoff, float sr) {  // BinauralDSP.cs:99-101
-  const float rc = 1.0f / (cutoff * kDoublePi);
-  const float dt = 1.0f / sr;
-  return rc / (rc + dt);
-}
-
-bool curve_ok(const art_curve& c) { return c.baked && c.sample_count >= 2; }
 
 // One lane per source; both channels. data: this source's interleaved frames.
 __global__ __launch_bounds__(kDspBlock) void dsp_kernel(float* __restrict__ data, const long long* __restrict__ offsets,
@@ -294,59 +264,88 @@ __global__ __launch_bounds__(64) void dsp_tiled_kernel(float* __restrict__ data,
 
 }  // namespace
 
-// Per-buffer scalars (everything the C# recomputes per sample is constant over the buffer).
+// Per-buffer scalars of one OnAudioFilterRead call (art_dsp_math.hpp has the operation sequence).
 int dsp_source_params(const art_spatializer_settings& st, const art_audio_source& src, int sample_rate,
                       art_dsp_source_params& p) {
   std::memset(&p, 0, sizeof p);
   if (src.channels != 2) { p.flags = 4; return ART_OK; }
   if (!curve_ok(st.reverb_volume_curve) || (src.muffle_strength > 0.0f && !curve_ok(st.muffle_curve)))
     return ART_E_INVALID;
-  const float sr = (float)sample_rate;
-  if (src.muffle_strength > 0.0f) {  // MuffleDSP.cs:22-26
-    const float muffle = curve_eval(st.muffle_curve, src.muffle_strength);
-    const float cutoff = ulerp(st.muffle_cutoff_max, st.muffle_cutoff_min, muffle);
-    p.muffle_alpha = lowpass_alpha(cutoff, sr);
-    p.flags |= 1;
-  }
-  {  // ReverbDSP.cs:12-13
-    const float t = curve_eval(st.reverb_volume_curve, src.reverb_volume);
-    p.dry_boost = ulerp(st.reverb_dry_boost_min, st.reverb_dry_boost_max, t);
-  }
-  {  // BinauralDSP.cs:17-50, :65, :73
-    const float* ld = src.local_dir;
-    const float dist = src.listener_distance;
-    // BinauralDSP.Process runs unbursted on the audio thread (no [BurstCompile] under Audio/), so
-    // Unity.Mathematics' atan2 / sin / cos are (float)System.Math.Atan2/Sin/Cos: double precision,
-    // rounded once to float.
-    const float azimuth = (float)std::atan2((double)ld[0], (double)ld[2]) * kToDegrees;
-    float eps = st.pan_strength;
-    if (st.distance_based_panning) eps *= usaturate(dist / st.max_pan_distance);
-    const float pan = (float)std::sin((double)(azimuth * kToRadians)) * eps;
-    const float gl = std::sqrt(0.5f * (1.0f - pan));
-    const float gr = std::sqrt(0.5f * (1.0f + pan));
-    const float front = umax(0.0f, (float)std::cos((double)(azimuth * kToRadians)));
-    float rear = ulerp(1.0f - st.rear_attenuation_strength, 1.0f, front);
-    if (st.distance_based_rear_attenuation) {
-      const float df = usaturate(1.0f - (dist / st.max_rear_attenuation_distance));
-      rear = uclamp(rear * df, 1.0f - st.rear_attenuation_strength, 1.0f);
-    }
-    const float elev = ld[1] <= 0.0f ? ulerp(1.0f, st.low_pass_volume, usaturate(-ld[1]))
-                                     : ulerp(1.0f, st.high_pass_volume, usaturate(ld[1]));
-    p.gain_left = gl * rear * elev;
-    p.gain_right = gr * rear * elev;
-    if (ld[1] <= 0.0f) {
-      const float c = ulerp(st.low_pass_cutoff_min, st.low_pass_cutoff_max, usaturate(-ld[1])) *
-                      (1.0f - 0.5f * usaturate(dist / st.max_elevation_effect_distance));
-      p.filter_alpha = lowpass_alpha(c, sr);
-      p.flags |= 2;
-    } else {
-      const float c = ulerp(st.high_pass_cutoff_min, st.high_pass_cutoff_max, usaturate(ld[1])) *
-                      (1.0f + 0.5f * usaturate(dist / st.max_elevation_effect_distance));
-      p.filter_alpha = highpass_alpha(c, sr);
-    }
-  }
-  p.volume = src.volume_multiplier;
+  DspSourceInputs in;
+  in.muffle_strength = src.muffle_strength;
+  in.reverb_volume = src.reverb_volume;
+  in.local_dir = mk3(src.local_dir[0], src.local_dir[1], src.local_dir[2]);
+  in.listener_distance = src.listener_distance;
+  in.volume_multiplier = src.volume_multiplier;
+  p = dsp_source_scalars(st, in, (float)sample_rate);
   return ART_OK;
+}
+
+// One source of the audio tick: the OnLateUpdate step on the frame's settings record, then the
+// per-buffer scalars. rec: the 24-B AudioTargetRTSettings record as six floats.
+ART_HD art_dsp_source_params tick_source(const art_spatializer_settings& st, float sr, const float rec[6],
+                                         const art_listener& l, vec3 target, float volume) {
+  DspSourceInputs in;
+  in.muffle_strength = rec[0];
+  in.reverb_volume = rec[2];
+  listener_local(l, mk3(rec[3], rec[4], rec[5]), target, in.local_dir, in.listener_distance);
+  in.volume_multiplier = volume;
+  return dsp_source_scalars(st, in, sr);
+}
+
+int dsp_tick_params_host(const art_spatializer_settings& st, int sample_rate, const art_listener* listeners,
+                         const art_fan* fans, int fan_count, const float* targets, int T, const float* volume,
+                         art_dsp_source_params* out) {
+  if (!curve_ok(st.reverb_volume_curve) || !curve_ok(st.muffle_curve)) return ART_E_INVALID;
+  for (int f = 0; f < fan_count; ++f) {
+    if (!fans[f].settings) return ART_E_INVALID;
+    for (int t = 0; t < T; ++t) {
+      float rec[6];
+      std::memcpy(rec, &fans[f].settings[t], sizeof rec);
+      const size_t s = (size_t)f * T + t;
+      out[s] = tick_source(st, (float)sample_rate, rec, listeners[f], mk3(targets[3 * t], targets[3 * t + 1], targets[3 * t + 2]),
+                           volume ? volume[s] : 1.0f);
+    }
+  }
+  return ART_OK;
+}
+
+namespace {
+
+// The audio tick's parameter step, one lane per source s = f * T + t: the settings record of the
+// frame's result block, the fan's listener, the bound scene's target position and the bound curves
+// in, one art_dsp_source_params record out. The block is only read; the settings are assumed
+// aligned to 4 bytes only (8-B loads when the record's address allows, the layout's 16-B strides
+// always do).
+__global__ __launch_bounds__(kDspBlock) void dsp_tick_params_kernel(DspTickArgs a) {
+  const int s = blockIdx.x * kDspBlock + threadIdx.x;
+  if (s >= a.count) return;
+  const int f = s / a.T, t = s - f * a.T;
+  const uint8_t* rp = a.block + (size_t)f * a.stride + a.settings_off + (size_t)t * sizeof(art_target_settings);
+  float rec[6];
+  if ((reinterpret_cast<uintptr_t>(rp) & 7) == 0) {
+    const float2* r2 = reinterpret_cast<const float2*>(rp);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float2 v = r2[k];
+      rec[2 * k] = v.x;
+      rec[2 * k + 1] = v.y;
+    }
+  } else {
+    const float* r1 = reinterpret_cast<const float*>(rp);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rec[k] = r1[k];
+  }
+  const art_listener l = a.listeners[f];
+  const vec3 target = mk3(a.targets[3 * t], a.targets[3 * t + 1], a.targets[3 * t + 2]);
+  a.out[s] = tick_source(a.st, a.sr, rec, l, target, a.volume ? a.volume[s] : 1.0f);
+}
+
+}  // namespace
+
+void launch_dsp_tick_params(const DspTickArgs& a, hipStream_t st) {
+  if (a.count <= 0) return;
+  hipLaunchKernelGGL(dsp_tick_params_kernel, dim3((a.count + kDspBlock - 1) / kDspBlock), dim3(kDspBlock), 0, st, a);
 }
 
 void launch_dsp(float* data, unsigned long long data_bytes, const long long* offsets, const int* frames_of,

@@ -104,4 +104,110 @@ ART_API int art_dsp_process_device(art_ctx* c, float* d_data, const art_dsp_sour
   return ART_OK;
 }
 
+// ---------------------------------------------------------------------------- audio tick
+ART_API int art_dsp_tick_params_host(const art_spatializer_settings* settings, int32_t sample_rate,
+                                     const art_listener* listeners, const art_fan* fans, int32_t fan_count,
+                                     const float* target_positions, int32_t target_count, const float* volume,
+                                     art_dsp_source_params* out) {
+  if (!settings || sample_rate <= 0 || fan_count < 0 || target_count < 0) return ART_E_INVALID;
+  if (fan_count > 0 && (!listeners || !fans || (target_count > 0 && (!target_positions || !out)))) return ART_E_INVALID;
+  return dsp_tick_params_host(*settings, sample_rate, listeners, fans, fan_count, target_positions, target_count, volume, out);
+}
+
+ART_API int art_dsp_settings_bind(art_ctx* c, const art_spatializer_settings* settings, int32_t sample_rate) {
+  if (!c) return ART_E_INVALID;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
+  if (!settings || sample_rate <= 0) return fail(c, ART_E_INVALID, "invalid argument");
+  const art_curve& mc = settings->muffle_curve;
+  const art_curve& rc = settings->reverb_volume_curve;
+  if (!mc.baked || mc.sample_count < 2 || !rc.baked || rc.sample_count < 2)
+    return fail(c, ART_E_INVALID, "art_dsp_settings_bind: both curves need a baked table of at least 2 samples");
+  if (c->inflight) return fail(c, ART_E_STATE, "a frame is in flight");
+  if (c->devs.empty()) return fail(c, ART_E_STATE, "the context has no device");
+  Device& dv = c->devs[0];
+  HIP_TRY(c, hipSetDevice(dv.id));
+  // a tick still running on the caller's stream reads the curves being replaced
+  if (int rc2 = dv.fence.wait(c, dv.stream)) return rc2;
+  HIP_TRY(c, hipStreamSynchronize(dv.stream));
+  c->tick.bound = false;
+  const size_t nm = (size_t)mc.sample_count, nr = (size_t)rc.sample_count;
+  if (!dv.tick_curves.reserve((nm + nr) * sizeof(float))) return fail(c, ART_E_NOMEM, "device allocation failed");
+  float* d = static_cast<float*>(dv.tick_curves.p);
+  HIP_TRY(c, hipMemcpy(d, mc.baked, nm * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d + nm, rc.baked, nr * sizeof(float), hipMemcpyHostToDevice));
+  c->tick.st = *settings;
+  c->tick.st.muffle_curve.baked = d;
+  c->tick.st.reverb_volume_curve.baked = d + nm;
+  c->tick.sample_rate = sample_rate;
+  c->tick.bound = true;
+  return ART_OK;
+}
+
+// The parameter step of the tick on `st`, ordered as a reader of the bound scene; count_out: sources.
+static int tick_params(art_ctx* c, const char* fn, const void* d_block, uint32_t out_flags, int32_t fan_count,
+                       const art_listener* d_listeners, const float* d_volume, art_dsp_source_params* d_params,
+                       bool more_null, hipStream_t st, int& count_out) {
+  if (!c) return ART_E_INVALID;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", fn);
+  if (c->inflight) return fail(c, ART_E_STATE, "%s: a frame is in flight (tick after art_complete)", fn);
+  if (c->devs.empty() || !c->devs[0].bound) return fail(c, ART_E_STATE, "%s: no scene bound (art_scene_bind)", fn);
+  if (!c->tick.bound) return fail(c, ART_E_STATE, "%s: no spatializer settings bound (art_dsp_settings_bind)", fn);
+  const Frame& f = c->fr;
+  if (!(f.stages & ART_STAGE_REDUCE)) return fail(c, ART_E_INVALID, "%s: the bound frame has no ART_STAGE_REDUCE (no settings section)", fn);
+  if (fan_count < 0 || (fan_count > 0 && (!d_block || !d_listeners || !d_params || more_null)))
+    return fail(c, ART_E_INVALID, "%s: bad device buffers", fn);
+  count_out = 0;
+  if (fan_count == 0) return ART_OK;
+  Device& dv = c->devs[0];
+  if (dv.sc.T != f.T || !dv.sc.targets) return fail(c, ART_E_STATE, "%s: the bound scene's targets are not the frame's", fn);
+  if ((long long)fan_count * f.T > 0x7fffffffLL) return fail(c, ART_E_UNSUPPORTED, "%s: more than 2^31 - 1 sources", fn);
+  HIP_TRY(c, hipSetDevice(dv.id));
+  // the bound frame's layout for the requested outputs (as art_launch_device derives it)
+  art_frame_desc tmp{};
+  tmp.ray_count = f.R; tmp.max_hits_per_ray = f.H; tmp.audio_target_count = f.T; tmp.batch_slots = f.TC;
+  tmp.stages = f.stages;
+  const FanLayout L = make_layout(&tmp, out_flags);
+  DspTickArgs a{};
+  a.block = static_cast<const uint8_t*>(d_block);
+  a.stride = L.stride;
+  a.settings_off = L.settings_off;
+  a.T = f.T;
+  a.count = fan_count * f.T;
+  a.listeners = d_listeners;
+  a.targets = dv.sc.targets;
+  a.volume = d_volume;
+  a.out = d_params;
+  a.st = c->tick.st;
+  a.sr = (float)c->tick.sample_rate;
+  int rc = scene_reader_begin(c, dv, f, st);
+  if (rc) return rc;
+  launch_dsp_tick_params(a, st);
+  HIP_TRY(c, hipGetLastError());
+  count_out = a.count;
+  return scene_reader_end(c, dv, st);
+}
+
+ART_API int art_dsp_tick_params_device(art_ctx* c, const void* d_block, uint32_t out_flags, int32_t fan_count,
+                                       const art_listener* d_listeners, const float* d_volume,
+                                       art_dsp_source_params* d_params, void* stream) {
+  int count = 0;
+  return tick_params(c, __func__, d_block, out_flags, fan_count, d_listeners, d_volume, d_params, false,
+                     static_cast<hipStream_t>(stream), count);
+}
+
+ART_API int art_dsp_tick_device(art_ctx* c, const void* d_block, uint32_t out_flags, int32_t fan_count,
+                                const art_listener* d_listeners, const float* d_volume, float* d_data,
+                                art_dsp_state* d_state, int32_t frames, art_dsp_source_params* d_params, void* stream) {
+  if (c && !c->cpu && frames < 0) return fail(c, ART_E_INVALID, "%s: frames is negative", __func__);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int count = 0;
+  int rc = tick_params(c, __func__, d_block, out_flags, fan_count, d_listeners, d_volume, d_params,
+                       frames > 0 && (!d_data || !d_state), st, count);
+  if (rc || count == 0 || frames == 0) return rc;
+  launch_dsp(d_data, (unsigned long long)count * (unsigned long long)frames * 8ull, nullptr, nullptr, frames, d_params,
+             d_state, count, st);
+  HIP_TRY(c, hipGetLastError());
+  return ART_OK;
+}
+
 }  // extern "C"

@@ -152,6 +152,22 @@ int dsp_source_params(const art_spatializer_settings& st, const art_audio_source
                       art_dsp_source_params& p);
 void launch_dsp(float* data, unsigned long long data_bytes, const long long* offsets, const int* frames_of,
                 int frames_all, const art_dsp_source_params* params, art_dsp_state* state, int count, hipStream_t st);
+// The audio tick's parameter step (art_dsp_tick_*): source s = f * T + t reads the settings record at
+// block + f * stride + settings_off + 24 t, listeners[f], targets[3 t ..] and volume[s] (or 1).
+int dsp_tick_params_host(const art_spatializer_settings& st, int sample_rate, const art_listener* listeners,
+                         const art_fan* fans, int fan_count, const float* targets, int T, const float* volume,
+                         art_dsp_source_params* out);
+struct DspTickArgs {
+  const uint8_t* block; uint32_t stride, settings_off;
+  int T, count;                   // count = fan_count * T sources
+  const art_listener* listeners;  // [fan_count]
+  const float* targets;           // float3[T]: the bound scene's
+  const float* volume;            // [count] or nullptr
+  art_dsp_source_params* out;     // [count]
+  art_spatializer_settings st;    // the curves' baked tables are device arrays
+  float sr;
+};
+void launch_dsp_tick_params(const DspTickArgs& a, hipStream_t st);
 
 // Dirty records of a resident-store sync (art_colliders_sync): the update image (indices and
 // records per kind) and the resident lists and decoded records they are scattered into.

@@ -33,6 +33,29 @@ int LaunchFence::wait(art_ctx* c, hipStream_t waiter) {
   return ART_OK;
 }
 
+// A reader of the bound scene enqueued on the caller's stream st (a device frame, the audio tick).
+// Before it: st waits for the resident store's last sync and for the previous reader when they ran
+// on other streams (frames also share the context's accumulators and pair buffers; on the same
+// stream, stream order already does).
+int scene_reader_begin(art_ctx* c, Device& dv, const Frame& f, hipStream_t st) {
+  if ((f.resident || f.res_targets) && dv.store.done && st != dv.store.stream) HIP_TRY(c, hipStreamWaitEvent(st, dv.store.done, 0));
+  if (dv.fence.pending && st != dv.fence.stream) {
+    int rc = dv.fence.mark_done(c);
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamWaitEvent(st, dv.fence.done, 0));
+  }
+  return ART_OK;
+}
+// After it: the next sync, bind or schedule rewrites the scene or reuses the shared buffers on
+// dv.stream after this reader (LaunchFence::wait records the event on st then).
+int scene_reader_end(art_ctx* c, Device& dv, hipStream_t st) {
+  dv.fence.pending = true;
+  dv.fence.stream = st;
+  dv.fence.recorded = false;
+  if (c->flags & ART_CTX_EVENT_EACH_LAUNCH) return dv.fence.mark_done(c);  // opt-in: the caller may drop its stream after this call
+  return ART_OK;
+}
+
 int ensure_side(art_ctx* c, SideStream& s) {
   if (s.st) return ART_OK;
   HIP_TRY(c, hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));

@@ -17,6 +17,18 @@
  * processed in place, plus the filter state the C# structs keep between calls. The per-buffer
  * scalars (curve lookups, filter coefficients, binaural gains with atan2/sin/cos) are computed on
  * the host; the per-sample recurrences run on the GPU, one lane per source (both channels).
+ *
+ * The audio tick (art_dsp_tick_*) is the main-thread link between the two:
+ *   AudioTargetManager.UpdateAudioTargetSettings -> AudioSpatializer.UpdateSpatializer
+ *     -> OnLateUpdate                    Audio/AudioTarget/AudioSpatializer.cs:55-67
+ *        worldDir = PercievedAudioPosition - listener.position
+ *        cachedLocalDir = normalize(InverseTransformDirection(worldDir))
+ *        cachedListenerDistance = distance(transform.position, listener.position)
+ * followed by the per-buffer scalars above. It turns the settings section of a frame's result blocks
+ * (art_launch_device, art_device.h) into art_dsp_source_params on the device, on the caller's
+ * stream and without a host round trip; art_dsp_tick_params_host is the same computation on the
+ * host. InverseTransformDirection is engine-native: the contract is math.mul(math.inverse(q), v)
+ * with q the listener's rotation (rotation only).
  */
 #ifndef ART_DSP_H
 #define ART_DSP_H
@@ -93,6 +105,41 @@ ART_API int art_dsp_source_params_get(const art_spatializer_settings* settings, 
  * d_state (art_dsp_state[count]) are device arrays. Enqueued on `stream`, not synchronised. */
 ART_API int art_dsp_process_device(art_ctx* ctx, float* d_data, const art_dsp_source_params* d_params,
                                    art_dsp_state* d_state, int32_t count, int32_t frames, void* stream);
+
+/* ---- audio tick (ABI 3.5): spatializer parameters from a frame's result blocks ---------------- */
+
+/* The AudioListener's transform (one per fan): position, rotation as a quaternion (x, y, z, w). */
+typedef struct { float position[3]; float rotation[4]; } art_listener;   /* 28 B; one per fan */
+
+/* Host twin, context-free (works with the CPU backend's frames and in tests): source s = f*T + t,
+ * out[f*T + t] from fans[f].settings[t], listeners[f] and target_positions[3*t..] (the bound scene's
+ * target positions, the JobBatch snapshot); volume = float[fan_count*T], NULL = 1.0f.
+ * Both curves must be valid (baked, sample_count >= 2), else ART_E_INVALID. */
+ART_API int art_dsp_tick_params_host(const art_spatializer_settings* settings, int32_t sample_rate,
+        const art_listener* listeners, const art_fan* fans, int32_t fan_count,
+        const float* target_positions, int32_t target_count,
+        const float* volume, art_dsp_source_params* out);
+
+/* Copy the scalars, upload the two baked curves to the context's first device; synchronous.
+ * Both curves must be valid, else ART_E_INVALID (the device cannot refuse a single source). */
+ART_API int art_dsp_settings_bind(art_ctx* ctx, const art_spatializer_settings* settings, int32_t sample_rate);
+
+/* d_block / out_flags / fan_count as given to art_launch_device; d_listeners = art_listener[fan_count],
+ * d_volume = float[fan_count*T] or NULL, d_params = art_dsp_source_params[fan_count*T] (all HBM).
+ * Enqueued on `stream`, not synchronised. The block is only read. The tick reads the bound scene's
+ * target positions, so it is ordered like a frame: after the last art_targets_sync, after a frame on
+ * another stream, and a later sync, bind or schedule orders itself after it.
+ * ART_E_STATE without a bound scene or bound settings or while a host frame is in flight;
+ * ART_E_INVALID for a bound frame without ART_STAGE_REDUCE (no settings section). */
+ART_API int art_dsp_tick_params_device(art_ctx* ctx, const void* d_block, uint32_t out_flags, int32_t fan_count,
+        const art_listener* d_listeners, const float* d_volume, art_dsp_source_params* d_params, void* stream);
+
+/* The step above, then the per-sample chain over d_data = float[fan_count*T][frames][2] and
+ * d_state[fan_count*T]; d_params is written (callers may read it back). Two launches on `stream`,
+ * no host work between them. */
+ART_API int art_dsp_tick_device(art_ctx* ctx, const void* d_block, uint32_t out_flags, int32_t fan_count,
+        const art_listener* d_listeners, const float* d_volume, float* d_data, art_dsp_state* d_state,
+        int32_t frames, art_dsp_source_params* d_params, void* stream);
 
 #ifdef __cplusplus
 }

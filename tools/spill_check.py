@@ -23,11 +23,11 @@ with tempfile.TemporaryDirectory() as d:
     import glob
     asm = open(glob.glob(f"{d}/*gfx950.s")[0]).read().splitlines()
 
-kernels, cur = [], None
+kernels, cur, last = [], None, None
 for i, line in enumerate(asm):
     m = re.match(r"^(_Z\S+):\s*;\s*@", line)
     if m:
-        cur = {"name": m.group(1), "lines": []}
+        cur = last = {"name": m.group(1), "lines": [], "res": {}}
         kernels.append(cur)
         continue
     if cur is not None:
@@ -35,9 +35,13 @@ for i, line in enumerate(asm):
             cur = None
         else:
             cur["lines"].append(line)
+    elif last is not None:  # the resource comments that follow a kernel's code
+        m = re.match(r"^; (NumVgprs|ScratchSize|LDSByteSize): (\d+)", line)
+        if m:
+            last["res"].setdefault(m.group(1), int(m.group(2)))
 
 def demangle(n):
-    return subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip().split("(")[0]
+    return subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "").split("(")[0]
 
 for k in kernels:
     loop = "not in a loop"
@@ -52,6 +56,10 @@ for k in kernels:
             off = re.search(r"offset:(\d+)", line)
             sites.append((m.group(1), int(off.group(1)) if off else 0, loop))
     name = demangle(k["name"])
+    if k["res"]:  # every kernel: registers, scratch and LDS as the compiler reports them
+        r = k["res"]
+        print(f"{name[:160]}: {r.get('NumVgprs', '?')} VGPRs, scratch {r.get('ScratchSize', '?')} B, "
+              f"LDS {r.get('LDSByteSize', '?')} B")
     if not sites:
         continue
     print(f"{name[:160]}: {len(sites)} scratch ops")
