@@ -243,6 +243,9 @@ SIGNATURES = {
     "art_dsp_settings_bind": (I32, [VP, C.POINTER(art_spatializer_settings), I32]),
     "art_dsp_tick_params_device": (I32, [VP, VP, U32, I32, VP, VP, VP, VP]),
     "art_dsp_tick_device": (I32, [VP, VP, U32, I32, VP, VP, VP, VP, I32, VP, VP]),
+    "art_dsp_mix_device": (I32, [VP, VP, VP, VP, I32, I32, I32, VP, VP]),
+    "art_dsp_tick_mix_device": (I32, [VP, VP, U32, I32, VP, VP, VP, VP, I32, VP, VP, VP]),
+    "art_dsp_mix_host": (I32, [VP, VP, VP, I32, I32, I32, VP]),
     # art_colliders.h
     "art_collider_add": (I32, [VP, I32, VP, C.POINTER(I32)]),
     "art_collider_set": (I32, [VP, I32, I32, VP]),

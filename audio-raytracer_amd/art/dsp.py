@@ -9,6 +9,10 @@ The audio tick (tick_params_host, bind_settings, tick_params_device, tick_device
 link in front of it (AudioSpatializer.UpdateSpatializer / OnLateUpdate, AudioSpatializer.cs:55-67):
 the settings section of a frame's result blocks and each fan's listener become the per-buffer
 scalars, on the device and on the caller's stream, or on the host.
+
+The listener mix (mix_device, tick_mix_device, mix_host) is the server form of the chain: one dry
+buffer per audio target in, shared by every fan, and one mix per fan out, the fan's T sources summed
+in ascending target order (include/art_dsp.h has the contract).
 """
 from __future__ import annotations
 
@@ -197,3 +201,41 @@ def tick_device(ctx, d_block, fan_count: int, d_listeners, d_data, d_state, fram
                                      _dptr(d_data), _dptr(d_state), frames, _dptr(d_params), stream)
     if rc:
         ctx._raise(rc)
+
+
+def mix_device(ctx, d_dry, d_params, d_state, fan_count: int, target_count: int, frames: int, d_mix,
+               stream: int | None = None):
+    """art_dsp_mix_device on `stream` (not synchronised): d_dry float [T][frames][2] (only read),
+    d_params / d_state [fan_count * T], d_mix float [fan_count][frames][2] (overwritten)."""
+    rc = ctx.lib.art_dsp_mix_device(ctx.ptr, _dptr(d_dry), _dptr(d_params), _dptr(d_state), fan_count, target_count, frames,
+                                    _dptr(d_mix), stream)
+    if rc:
+        ctx._raise(rc)
+
+
+def tick_mix_device(ctx, d_block, fan_count: int, d_listeners, d_dry, d_state, frames: int, d_params, d_mix, d_volume=None,
+                    out_flags: int = 0, stream: int | None = None):
+    """art_dsp_tick_mix_device on `stream` (not synchronised): the parameter step, then the listener
+    mix over d_dry (float [T][frames][2]) into d_mix (float [fan_count][frames][2])."""
+    rc = ctx.lib.art_dsp_tick_mix_device(ctx.ptr, _dptr(d_block), out_flags, fan_count, _dptr(d_listeners), _dptr(d_volume),
+                                         _dptr(d_dry), _dptr(d_state), frames, _dptr(d_params), _dptr(d_mix), stream)
+    if rc:
+        ctx._raise(rc)
+
+
+def mix_host(params: np.ndarray, state: np.ndarray, dry: np.ndarray, fan_count: int, target_count: int) -> np.ndarray:
+    """art_dsp_mix_host: params (abi.DSP_SOURCE_PARAMS [fan_count * T]), state (abi.DSP_STATE
+    [fan_count * T], updated in place), dry (float32 [T, frames * 2], only read); returns the mix,
+    float32 [fan_count, frames * 2]."""
+    n = fan_count * target_count
+    assert params.dtype == abi.DSP_SOURCE_PARAMS and params.size == n and params.flags["C_CONTIGUOUS"]
+    assert state.dtype == abi.DSP_STATE and state.size == n and state.flags["C_CONTIGUOUS"]
+    d = np.ascontiguousarray(dry, np.float32).reshape(target_count, -1)
+    frames = d.shape[1] // 2
+    assert d.shape[1] == 2 * frames
+    mix = np.zeros((fan_count, 2 * frames), np.float32)
+    rc = abi.load_library().art_dsp_mix_host(params.ctypes.data, state.ctypes.data, d.ctypes.data, fan_count, target_count,
+                                             frames, mix.ctypes.data)
+    if rc:
+        raise ValueError(f"art_dsp_mix_host: {abi.ERROR_NAMES.get(rc, rc)}")
+    return mix

@@ -46,8 +46,9 @@ namespace {
 // 3.1: ART_CTX_EVENT_EACH_LAUNCH, art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*;
 // 3.3: art_debug_echo_decided; 3.4: the resident target store (art_target_*, art_targets_*,
 // ART_CTX_RESIDENT_TARGETS, art_debug_cells_arena); 3.5: the audio tick (art_listener,
-// art_dsp_tick_params_host, art_dsp_settings_bind, art_dsp_tick_params_device, art_dsp_tick_device)
-constexpr uint32_t kAbiVersion = (3u << 16) | 5u;
+// art_dsp_tick_params_host, art_dsp_settings_bind, art_dsp_tick_params_device, art_dsp_tick_device);
+// 3.6: the listener mix (art_dsp_mix_device, art_dsp_tick_mix_device, art_dsp_mix_host)
+constexpr uint32_t kAbiVersion = (3u << 16) | 6u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {

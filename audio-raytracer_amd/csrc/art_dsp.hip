@@ -110,57 +110,23 @@ constexpr int kLoads = kTS * kTF / 64;  // float2 loads per lane per tile
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-struct Chain {
-  float pm, pl, ph, pi;  // previousMuffle, previousLP, previousHP, previousInput of this channel
-};
+// Chain and step<M> (the per-sample operation sequence of one channel): art_dsp_math.hpp.
 
-// M: bit 0 muffle, bit 1 low pass (fixed for the wave); M == 4: per-lane selects (exact: every
-// selected value is computed with the same operations as in the fixed variants).
+// n frames of one channel's chain from LDS row `in` to LDS row `out` (the same row in
+// dsp_tiled_kernel; a shared dry row and the source's own wet row in dsp_mix_kernel).
 template <int M>
-__device__ __forceinline__ float step(float x, const art_dsp_source_params& p, float gain, bool mf, bool lp,
-                                      Chain& c) {
-  if constexpr (M == 4) {
-    const float m = c.pm + p.muffle_alpha * (x - c.pm);
-    x = mf ? m : x;
-    c.pm = mf ? m : c.pm;
-  } else if constexpr (M & 1) {
-    c.pm = c.pm + p.muffle_alpha * (x - c.pm);  // MuffleDSP.LowPass :43-44
-    x = c.pm;
-  }
-  x = x * p.dry_boost;  // ReverbDSP :21-22
-  x = x * gain;         // BinauralDSP :59-60
-  if constexpr (M == 4) {
-    const float l = c.pl + p.filter_alpha * (x - c.pl);
-    const float h = p.filter_alpha * (c.ph + x - c.pi);
-    c.pl = lp ? l : c.pl;
-    c.ph = lp ? c.ph : h;
-    c.pi = lp ? c.pi : x;
-    x = lp ? l : h;
-  } else if constexpr (M & 2) {
-    c.pl = c.pl + p.filter_alpha * (x - c.pl);  // LowPass :92-93
-    x = c.pl;
-  } else {
-    const float h = p.filter_alpha * (c.ph + x - c.pi);  // HighPass :102-105
-    c.pi = x;
-    c.ph = h;
-    x = h;
-  }
-  return x * p.volume;  // AudioSpatializer.cs:84-85
-}
-
-template <int M>
-__device__ __forceinline__ void run_tile(float* row, int n, const art_dsp_source_params& p, float gain, bool mf,
-                                         bool lp, Chain& c) {
+__device__ __forceinline__ void run_tile(const float* in, float* out, int n, const art_dsp_source_params& p,
+                                         float gain, bool mf, bool lp, Chain& c) {
   if (n == kTF) {
     float x[kTF];
 #pragma unroll
-    for (int k = 0; k < kTF; ++k) x[k] = row[2 * k];
+    for (int k = 0; k < kTF; ++k) x[k] = in[2 * k];
 #pragma unroll
     for (int k = 0; k < kTF; ++k) x[k] = step<M>(x[k], p, gain, mf, lp, c);
 #pragma unroll
-    for (int k = 0; k < kTF; ++k) row[2 * k] = x[k];
+    for (int k = 0; k < kTF; ++k) out[2 * k] = x[k];
   } else {
-    for (int k = 0; k < n; ++k) row[2 * k] = step<M>(row[2 * k], p, gain, mf, lp, c);
+    for (int k = 0; k < n; ++k) out[2 * k] = step<M>(in[2 * k], p, gain, mf, lp, c);
   }
 }
 
@@ -241,12 +207,12 @@ __global__ __launch_bounds__(64) void dsp_tiled_kernel(float* __restrict__ data,
     load(t + 1);  // past the last tile every offset is out of range: loads 0, no branch
     const int n = min(max(my_frames - t * kTF, 0), kTF);
     if (generic) {
-      run_tile<4>(row, n, p, gain, mf, lp, c);
+      run_tile<4>(row, row, n, p, gain, mf, lp, c);
     } else {
-      if (b0 && cls == 0) run_tile<0>(row, n, p, gain, mf, lp, c);
-      if (b1 && cls == 1) run_tile<1>(row, n, p, gain, mf, lp, c);
-      if (b2 && cls == 2) run_tile<2>(row, n, p, gain, mf, lp, c);
-      if (b3 && cls == 3) run_tile<3>(row, n, p, gain, mf, lp, c);
+      if (b0 && cls == 0) run_tile<0>(row, row, n, p, gain, mf, lp, c);
+      if (b1 && cls == 1) run_tile<1>(row, row, n, p, gain, mf, lp, c);
+      if (b2 && cls == 2) run_tile<2>(row, row, n, p, gain, mf, lp, c);
+      if (b3 && cls == 3) run_tile<3>(row, row, n, p, gain, mf, lp, c);
     }
     __syncthreads();
 #pragma unroll
@@ -262,7 +228,218 @@ __global__ __launch_bounds__(64) void dsp_tiled_kernel(float* __restrict__ data,
   }
 }
 
+// ---- listener mix: one dry buffer per target in, one mix per fan out -------------------------
+//
+// dsp_tiled_kernel's skeleton with shared input and summed output. Source s = f * T + t reads the
+// dry row of target t (float[T][frames][2], shared by every fan) and fan f's listener hears
+//   mix[f] = ((y[f,0] + y[f,1]) + ...) + y[f,T-1]     fp32, one add per target, ascending t,
+// starting from y[f,0] itself. A wave carries G = 32 / T whole fans (T <= 32; the 32 - G T left-over
+// source slots idle) or one fan in rounds of 32 targets (T > 32). Per tile of kTF frames:
+//   load   the round's dry rows, one 8-B-per-lane buffer load of kTF frames each, into LDS;
+//   chain  lane (slot, channel) runs its chain from dry row t (lanes of different fans read the same
+//          address: a broadcast) into its own padded wet row;
+//   mix    lane k takes frame k as a float2 and sums each fan's rows serially in target order (8-B
+//          LDS reads at unit lane stride), then one coalesced 8-B-per-lane store per fan.
+// Round r > 0 of a fan reads the mix back as the accumulator and continues the same serial chain
+// with targets 32 r .., so the bits are the definition's at any T. Only this wave wrote those bytes:
+// no atomics, no wait for another workgroup, nothing that depends on scheduling.
+__global__ __launch_bounds__(64) void dsp_mix_kernel(const float* __restrict__ dry,
+                                                     const art_dsp_source_params* __restrict__ params,
+                                                     art_dsp_state* __restrict__ state, float* mix, int F, int T,
+                                                     int frames, uint32_t dry_bytes, uint32_t mix_bytes) {
+  __shared__ float lds[2 * kTS * kRow];
+  float* const dtile = lds;               // dry rows of the round (kTS rows)
+  float* const wtile = lds + kTS * kRow;  // one wet row per source slot
+  const int lane = threadIdx.x;
+  const int sl = lane >> 1, ch = lane & 1;
+  const int rowsT = min(T, kTS);  // targets per fan and round
+  const int G = kTS / rowsT;      // fans per wave (1 when T > 32)
+  const int g = sl / rowsT, tl = sl - g * rowsT;
+  const int f0 = blockIdx.x * G;
+  const int gcount = min(G, F - f0);  // fans of this wave (the last wave may be partial)
+  const int rounds = (T + kTS - 1) / kTS;
+  const int ntiles = (frames + kTF - 1) / kTF;
+  // buffer loads/stores with the hardware range check (as in dsp_tiled_kernel): an item past
+  // `frames` or past the round's rows gets the offset *_bytes: loads 0, store dropped
+  const __amdgpu_buffer_rsrc_t rd =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dry), 0, (int)dry_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(mix, 0, (int)mix_bytes, 0x00020000);
+  const int lf = lane & (kTF - 1);
+  const float* const in = dtile + tl * kRow + ch;
+  float* const out = wtile + sl * kRow + ch;
+
+  for (int r = 0; r < rounds; ++r) {
+    const int t0 = r * kTS;
+    const int nrows = min(T - t0, kTS);  // dry rows of the round = rows per fan in the mix pass
+    const bool active = g < gcount && tl < nrows;
+    const size_t s = (size_t)(f0 + g) * T + t0 + tl;
+    art_dsp_source_params p{};
+    Chain c{};
+    bool pass = false, run = false;
+    if (active) {
+      p = params[s];
+      pass = (p.flags & 4) != 0;  // not stereo: the dry frames as they are, the state kept (AudioSpatializer.cs:72)
+      run = !pass;
+      if (run) {
+        const float* sv = reinterpret_cast<const float*>(state + s);
+        c.pm = sv[0 + ch]; c.pl = sv[2 + ch]; c.ph = sv[4 + ch]; c.pi = sv[6 + ch];
+      }
+    }
+    const bool mf = (p.flags & 1) != 0, lp = (p.flags & 2) != 0;
+    const float gain = ch ? p.gain_right : p.gain_left;
+    const int cls = run ? (p.flags & 3) : -1;
+    const uint64_t b0 = __ballot(cls == 0), b1 = __ballot(cls == 1), b2 = __ballot(cls == 2), b3 = __ballot(cls == 3);
+    const bool generic = (b0 != 0) + (b1 != 0) + (b2 != 0) + (b3 != 0) >= 3;
+    const bool any_pass = __ballot(pass) != 0;
+    // a round reads what this wave's earlier rounds stored: those stores have completed
+    if (r > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+    // loader view: item i of this lane is frame lane % kTF of dry row kSPI * i + lane / kTF
+    u32x2 pre[kLoads];
+    auto load = [&](int tile) {
+      const int fr = tile * kTF + lf;
+#pragma unroll
+      for (int i = 0; i < kLoads; ++i) {
+        const int row = kSPI * i + lane / kTF;
+        const uint32_t off =
+            (row < nrows && fr < frames) ? ((uint32_t)(t0 + row) * (uint32_t)frames + (uint32_t)fr) * 8u : dry_bytes;
+        pre[i] = __builtin_amdgcn_raw_buffer_load_b64(rd, off, 0, 0);
+      }
+    };
+    load(0);
+    for (int tile = 0; tile < ntiles; ++tile) {
+#pragma unroll
+      for (int i = 0; i < kLoads; ++i)
+        *reinterpret_cast<u32x2*>(dtile + (kSPI * i + lane / kTF) * kRow + 2 * lf) = pre[i];
+      __syncthreads();  // also: the previous tile's mix pass has read the wet rows
+      load(tile + 1);   // past the last tile every offset is out of range: loads 0, no branch
+      const int n = min(frames - tile * kTF, kTF);
+      if (any_pass && pass)
+        for (int k = 0; k < n; ++k) out[2 * k] = in[2 * k];
+      const int nr = run ? n : 0;
+      if (generic) {
+        run_tile<4>(in, out, nr, p, gain, mf, lp, c);
+      } else {
+        if (b0 && cls == 0) run_tile<0>(in, out, nr, p, gain, mf, lp, c);
+        if (b1 && cls == 1) run_tile<1>(in, out, nr, p, gain, mf, lp, c);
+        if (b2 && cls == 2) run_tile<2>(in, out, nr, p, gain, mf, lp, c);
+        if (b3 && cls == 3) run_tile<3>(in, out, nr, p, gain, mf, lp, c);
+      }
+      __syncthreads();
+      if (lane < kTF && rounds == 1) {  // mix pass: lane = frame of the tile, both channels
+        // T <= 32: all 32 rows' reads in flight at once, then the wave's fans one after the other
+        // (every branch is wave-uniform); rows past the wave's last fan are read and not used
+        const int fr = tile * kTF + lane;
+        float2 y[kTS];
+#pragma unroll
+        for (int i = 0; i < kTS; ++i) y[i] = *reinterpret_cast<const float2*>(wtile + i * kRow + 2 * lane);
+        const int used = gcount * nrows;
+        float2 acc = y[0];
+        int k = 0, gg = 0;
+#pragma unroll
+        for (int i = 0; i < kTS; ++i) {
+          if (i < used) {
+            if (k == 0) {
+              acc = y[i];  // the sum starts from y[f,0] itself
+            } else {
+              acc.x = acc.x + y[i].x;
+              acc.y = acc.y + y[i].y;
+            }
+            if (++k == nrows) {
+              const uint32_t off =
+                  fr < frames ? ((uint32_t)(f0 + gg) * (uint32_t)frames + (uint32_t)fr) * 8u : mix_bytes;
+              __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, acc), rm, off, 0, 0);
+              k = 0;
+              ++gg;
+            }
+          }
+        }
+      } else if (lane < kTF) {  // T > 32: one fan, round r's rows added to what the earlier rounds stored
+        const int fr = tile * kTF + lane;
+        for (int gg = 0; gg < gcount; ++gg) {
+          const float* w = wtile + gg * rowsT * kRow + 2 * lane;
+          const uint32_t off =
+              fr < frames ? ((uint32_t)(f0 + gg) * (uint32_t)frames + (uint32_t)fr) * 8u : mix_bytes;
+          float2 acc;
+          int k = 0;
+          if (r == 0) {
+            acc = *reinterpret_cast<const float2*>(w);  // the sum starts from y[f,0] itself
+            k = 1;
+          } else {  // this lane's own store of the previous round (same lane, same address). Cast whole:
+                    // with v.x / v.y taken apart the compiler emitted a 4-B load copied into both channels
+            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rm, off, 0, 0);
+            acc = __builtin_bit_cast(float2, v);
+          }
+          for (; k < nrows; ++k) {
+            const float2 y = *reinterpret_cast<const float2*>(w + k * kRow);
+            acc.x = acc.x + y.x;
+            acc.y = acc.y + y.y;
+          }
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, acc), rm, off, 0, 0);
+        }
+      }
+    }
+    if (run) {
+      float* sv = reinterpret_cast<float*>(state + s);
+      sv[0 + ch] = c.pm; sv[2 + ch] = c.pl; sv[4 + ch] = c.ph; sv[6 + ch] = c.pi;
+    }
+  }
+}
+
+// One source's chain over `frames` interleaved stereo frames, dry -> wet, from and to its state.
+template <int M>
+void host_chain(const art_dsp_source_params& p, art_dsp_state& st, const float* dry, int frames, float* wet) {
+  float* sv = reinterpret_cast<float*>(&st);
+  for (int ch = 0; ch < 2; ++ch) {
+    Chain c{sv[0 + ch], sv[2 + ch], sv[4 + ch], sv[6 + ch]};
+    const float gain = ch ? p.gain_right : p.gain_left;
+    for (int i = 0; i < frames; ++i) wet[2 * i + ch] = step<M>(dry[2 * i + ch], p, gain, false, false, c);
+    sv[0 + ch] = c.pm; sv[2 + ch] = c.pl; sv[4 + ch] = c.ph; sv[6 + ch] = c.pi;
+  }
+}
+
 }  // namespace
+
+// The listener mix's definition (art_dsp_mix_host), literally: each source's chain, then one fp32
+// add per target in ascending t, starting from y[f,0] itself.
+void dsp_mix_host(const art_dsp_source_params* params, art_dsp_state* state, const float* dry, int fan_count, int T,
+                  int frames, float* mix) {
+  std::vector<float> wet((size_t)frames * 2);
+  for (int f = 0; f < fan_count; ++f) {
+    float* m = mix + (size_t)f * frames * 2;
+    for (int t = 0; t < T; ++t) {
+      const size_t s = (size_t)f * T + t;
+      const art_dsp_source_params& p = params[s];
+      const float* d = dry + (size_t)t * frames * 2;
+      const float* y = wet.data();
+      if (p.flags & 4) {
+        y = d;  // not stereo: the dry frames as they are, the state kept (AudioSpatializer.cs:72)
+      } else {
+        switch (p.flags & 3) {
+          case 0: host_chain<0>(p, state[s], d, frames, wet.data()); break;
+          case 1: host_chain<1>(p, state[s], d, frames, wet.data()); break;
+          case 2: host_chain<2>(p, state[s], d, frames, wet.data()); break;
+          default: host_chain<3>(p, state[s], d, frames, wet.data()); break;
+        }
+      }
+      if (t == 0) {
+        std::memcpy(m, y, (size_t)frames * 8);
+      } else {
+        for (int i = 0; i < 2 * frames; ++i) m[i] = m[i] + y[i];
+      }
+    }
+  }
+}
+
+void launch_dsp_mix(const float* dry, const art_dsp_source_params* params, art_dsp_state* state, int fan_count, int T,
+                    int frames, float* mix, hipStream_t st) {
+  if (fan_count <= 0 || T <= 0 || frames <= 0) return;
+  const int G = T <= kTS ? kTS / T : 1;
+  hipLaunchKernelGGL(dsp_mix_kernel, dim3((fan_count + G - 1) / G), dim3(64), 0, st, dry, params, state, mix, fan_count,
+                     T, frames, (uint32_t)((unsigned long long)T * frames * 8ull),
+                     (uint32_t)((unsigned long long)fan_count * frames * 8ull));
+}
+
 
 // Per-buffer scalars of one OnAudioFilterRead call (art_dsp_math.hpp has the operation sequence).
 int dsp_source_params(const art_spatializer_settings& st, const art_audio_source& src, int sample_rate,

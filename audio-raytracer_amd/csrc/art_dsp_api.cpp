@@ -143,10 +143,29 @@ ART_API int art_dsp_settings_bind(art_ctx* c, const art_spatializer_settings* se
   return ART_OK;
 }
 
+// What the listener mix asks of its buffers (dsp_mix_kernel's 8-B buffer operations with 32-bit byte
+// offsets); 0 or an error code, `why` set.
+static int mix_limits(const float* d_dry, const float* d_mix, long long fan_count, long long T, long long frames,
+                      const char*& why) {
+  if ((reinterpret_cast<uintptr_t>(d_dry) | reinterpret_cast<uintptr_t>(d_mix)) & 7) {
+    why = "d_dry and d_mix must be 8-byte aligned";
+    return ART_E_INVALID;
+  }
+  if (T * frames * 8 > 0x7fffffffLL || fan_count * frames * 8 > 0x7fffffffLL || fan_count * T > 0x7fffffffLL) {
+    why = "T * frames * 8 and fan_count * frames * 8 must stay below 2^31 bytes (split the call)";
+    return ART_E_UNSUPPORTED;
+  }
+  return ART_OK;
+}
+
+// The buffers of a listener mix that follows the parameter step (art_dsp_tick_mix_device): checked
+// with the other arguments, before anything is enqueued.
+struct TickMix { const float* d_dry; const float* d_mix; int32_t frames; };
+
 // The parameter step of the tick on `st`, ordered as a reader of the bound scene; count_out: sources.
 static int tick_params(art_ctx* c, const char* fn, const void* d_block, uint32_t out_flags, int32_t fan_count,
                        const art_listener* d_listeners, const float* d_volume, art_dsp_source_params* d_params,
-                       bool more_null, hipStream_t st, int& count_out) {
+                       bool more_null, hipStream_t st, int& count_out, const TickMix* mix = nullptr) {
   if (!c) return ART_E_INVALID;
   if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", fn);
   if (c->inflight) return fail(c, ART_E_STATE, "%s: a frame is in flight (tick after art_complete)", fn);
@@ -161,6 +180,10 @@ static int tick_params(art_ctx* c, const char* fn, const void* d_block, uint32_t
   Device& dv = c->devs[0];
   if (dv.sc.T != f.T || !dv.sc.targets) return fail(c, ART_E_STATE, "%s: the bound scene's targets are not the frame's", fn);
   if ((long long)fan_count * f.T > 0x7fffffffLL) return fail(c, ART_E_UNSUPPORTED, "%s: more than 2^31 - 1 sources", fn);
+  if (mix && mix->frames > 0) {
+    const char* why = nullptr;
+    if (int rc = mix_limits(mix->d_dry, mix->d_mix, fan_count, f.T, mix->frames, why)) return fail(c, rc, "%s: %s", fn, why);
+  }
   HIP_TRY(c, hipSetDevice(dv.id));
   // the bound frame's layout for the requested outputs (as art_launch_device derives it)
   art_frame_desc tmp{};
@@ -207,6 +230,50 @@ ART_API int art_dsp_tick_device(art_ctx* c, const void* d_block, uint32_t out_fl
   launch_dsp(d_data, (unsigned long long)count * (unsigned long long)frames * 8ull, nullptr, nullptr, frames, d_params,
              d_state, count, st);
   HIP_TRY(c, hipGetLastError());
+  return ART_OK;
+}
+
+// ---------------------------------------------------------------------------- listener mix
+ART_API int art_dsp_mix_device(art_ctx* c, const float* d_dry, const art_dsp_source_params* d_params,
+                               art_dsp_state* d_state, int32_t fan_count, int32_t target_count, int32_t frames,
+                               float* d_mix, void* stream) {
+  if (!c) return ART_E_INVALID;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
+  if (fan_count < 0 || target_count < 0 || frames < 0) return fail(c, ART_E_INVALID, "%s: negative argument", __func__);
+  if (fan_count == 0 || frames == 0) return ART_OK;
+  if (target_count < 1) return fail(c, ART_E_INVALID, "%s: target_count must be at least 1", __func__);
+  if (!d_dry || !d_params || !d_state || !d_mix) return fail(c, ART_E_INVALID, "%s: bad device buffers", __func__);
+  const char* why = nullptr;
+  if (int rc = mix_limits(d_dry, d_mix, fan_count, target_count, frames, why)) return fail(c, rc, "%s: %s", __func__, why);
+  Device& dv = c->devs[0];
+  HIP_TRY(c, hipSetDevice(dv.id));
+  launch_dsp_mix(d_dry, d_params, d_state, fan_count, target_count, frames, d_mix, static_cast<hipStream_t>(stream));
+  HIP_TRY(c, hipGetLastError());
+  return ART_OK;
+}
+
+ART_API int art_dsp_tick_mix_device(art_ctx* c, const void* d_block, uint32_t out_flags, int32_t fan_count,
+                                    const art_listener* d_listeners, const float* d_volume, const float* d_dry,
+                                    art_dsp_state* d_state, int32_t frames, art_dsp_source_params* d_params,
+                                    float* d_mix, void* stream) {
+  if (c && !c->cpu && frames < 0) return fail(c, ART_E_INVALID, "%s: frames is negative", __func__);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int count = 0;
+  const TickMix mix{d_dry, d_mix, frames};
+  int rc = tick_params(c, __func__, d_block, out_flags, fan_count, d_listeners, d_volume, d_params,
+                       frames > 0 && (!d_dry || !d_state || !d_mix), st, count, &mix);
+  if (rc || count == 0 || frames == 0) return rc;
+  launch_dsp_mix(d_dry, d_params, d_state, fan_count, c->fr.T, frames, d_mix, st);
+  HIP_TRY(c, hipGetLastError());
+  return ART_OK;
+}
+
+ART_API int art_dsp_mix_host(const art_dsp_source_params* params, art_dsp_state* state, const float* dry,
+                             int32_t fan_count, int32_t target_count, int32_t frames, float* mix) {
+  if (fan_count < 0 || target_count < 0 || frames < 0) return ART_E_INVALID;
+  if (fan_count == 0 || frames == 0) return ART_OK;
+  if (target_count < 1 || !params || !state || !dry || !mix) return ART_E_INVALID;
+  dsp_mix_host(params, state, dry, fan_count, target_count, frames, mix);
   return ART_OK;
 }
 

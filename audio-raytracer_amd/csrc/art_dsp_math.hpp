@@ -1,7 +1,8 @@
 // art_dsp_math.hpp — the spatializer's per-buffer scalars (include/art_dsp.h), shared by the host
 // entry points (art_dsp_source_params_get, art_dsp_process, art_dsp_tick_params_host) and the device
 // tick (dsp_tick_params_kernel, art_dsp.hip), so both evaluate the reference's fp32 operation
-// sequences from one source.
+// sequences from one source; and the per-sample chain of one channel (Chain,
+// step<M>), shared by dsp_tiled_kernel, dsp_mix_kernel and the listener mix's host twin.
 #pragma once
 
 #include <math.h>
@@ -112,6 +113,46 @@ ART_HD art_dsp_source_params dsp_source_scalars(const art_spatializer_settings& 
   }
   p.volume = in.volume_multiplier;
   return p;
+}
+
+// ---- the per-sample chain of one channel (AudioSpatializer.OnAudioFilterRead's four passes fused) ----
+// One definition for dsp_tiled_kernel, dsp_mix_kernel and the host twin of the listener mix
+// (art_dsp_mix_host): all evaluate this operation sequence.
+struct Chain {
+  float pm, pl, ph, pi;  // previousMuffle, previousLP, previousHP, previousInput of this channel
+};
+
+// M: bit 0 muffle, bit 1 low pass (fixed for the caller's wave or source); M == 4: per-lane selects
+// (exact: every selected value is computed with the same operations as in the fixed variants).
+template <int M>
+ART_HD float step(float x, const art_dsp_source_params& p, float gain, bool mf, bool lp, Chain& c) {
+  if constexpr (M == 4) {
+    const float m = c.pm + p.muffle_alpha * (x - c.pm);
+    x = mf ? m : x;
+    c.pm = mf ? m : c.pm;
+  } else if constexpr (M & 1) {
+    c.pm = c.pm + p.muffle_alpha * (x - c.pm);  // MuffleDSP.LowPass :43-44
+    x = c.pm;
+  }
+  x = x * p.dry_boost;  // ReverbDSP :21-22
+  x = x * gain;         // BinauralDSP :59-60
+  if constexpr (M == 4) {
+    const float l = c.pl + p.filter_alpha * (x - c.pl);
+    const float h = p.filter_alpha * (c.ph + x - c.pi);
+    c.pl = lp ? l : c.pl;
+    c.ph = lp ? c.ph : h;
+    c.pi = lp ? c.pi : x;
+    x = lp ? l : h;
+  } else if constexpr (M & 2) {
+    c.pl = c.pl + p.filter_alpha * (x - c.pl);  // LowPass :92-93
+    x = c.pl;
+  } else {
+    const float h = p.filter_alpha * (c.ph + x - c.pi);  // HighPass :102-105
+    c.pi = x;
+    c.ph = h;
+    x = h;
+  }
+  return x * p.volume;  // AudioSpatializer.cs:84-85
 }
 
 }  // namespace art

@@ -168,6 +168,13 @@ struct DspTickArgs {
   float sr;
 };
 void launch_dsp_tick_params(const DspTickArgs& a, hipStream_t st);
+// The listener mix (art_dsp_mix_*): source s = f * T + t runs its chain over dry[t] (float[T][frames][2],
+// only read); mix[f] (float[fan_count][frames][2]) = the fan's T results summed in ascending t.
+// The device form needs 8-B aligned dry / mix and T * frames * 8, fan_count * frames * 8 < 2^31.
+void dsp_mix_host(const art_dsp_source_params* params, art_dsp_state* state, const float* dry, int fan_count, int T,
+                  int frames, float* mix);
+void launch_dsp_mix(const float* dry, const art_dsp_source_params* params, art_dsp_state* state, int fan_count, int T,
+                    int frames, float* mix, hipStream_t st);
 
 // Dirty records of a resident-store sync (art_colliders_sync): the update image (indices and
 // records per kind) and the resident lists and decoded records they are scattered into.

@@ -141,6 +141,41 @@ ART_API int art_dsp_tick_device(art_ctx* ctx, const void* d_block, uint32_t out_
         const art_listener* d_listeners, const float* d_volume, float* d_data, art_dsp_state* d_state,
         int32_t frames, art_dsp_source_params* d_params, void* stream);
 
+/* ---- listener mix (ABI 3.6): one dry buffer per target in, one mix per fan out ------------------ */
+
+/* A server with one listener per fan: the scene's T audio targets are shared by every fan, so there
+ * is one dry buffer per target and tick, and a listener hears the sum of its T sources. Sources are
+ * numbered s = f*T + t as in the tick. For fan f, frame i, channel c:
+ *   y[f,t][i][c] = the per-sample chain (muffle, reverb, binaural, volume, as art_dsp_process_device
+ *                  runs it) over dry[t][.][c] with params[s], continuing from state[s]
+ *   mix[f][i][c] = (((y[f,0] + y[f,1]) + y[f,2]) + ... + y[f,T-1])[i][c]
+ * The adds are fp32, one per target, in ascending t, starting from y[f,0] itself (a -0.0f survives
+ * at T = 1), never contracted. state[s] afterwards is what art_dsp_process_device leaves for the
+ * same source and input; dry is only read; mix is overwritten. A source whose params carry flag bit
+ * 2 (not stereo; the tick never produces it) contributes its dry frames unchanged and keeps its
+ * state (AudioSpatializer.cs:72). Unity's mixer is closed: this order is the project's definition
+ * (DESIGN.md 3a).
+ *
+ * d_dry float[T][frames][2], d_params / d_state [fan_count*T], d_mix float[fan_count][frames][2];
+ * enqueued on `stream`, not synchronised. ART_OK and no launch for fan_count == 0 or frames == 0;
+ * otherwise ART_E_INVALID for target_count < 1, a NULL buffer, or d_dry / d_mix not 8-byte aligned,
+ * and ART_E_UNSUPPORTED when target_count*frames*8 or fan_count*frames*8 reaches 2^31 bytes. */
+ART_API int art_dsp_mix_device(art_ctx* ctx, const float* d_dry, const art_dsp_source_params* d_params,
+        art_dsp_state* d_state, int32_t fan_count, int32_t target_count, int32_t frames,
+        float* d_mix, void* stream);
+
+/* art_dsp_tick_params_device, then the above with T = the bound frame's: two launches on
+ * `stream`, no host work between them; same ordering rules and errors as art_dsp_tick_device,
+ * and art_dsp_mix_device's for d_dry / d_mix (checked before anything is enqueued). */
+ART_API int art_dsp_tick_mix_device(art_ctx* ctx, const void* d_block, uint32_t out_flags, int32_t fan_count,
+        const art_listener* d_listeners, const float* d_volume, const float* d_dry,
+        art_dsp_state* d_state, int32_t frames, art_dsp_source_params* d_params,
+        float* d_mix, void* stream);
+
+/* Host twin, context-free (works beside the CPU backend): the contract above, literally. */
+ART_API int art_dsp_mix_host(const art_dsp_source_params* params, art_dsp_state* state, const float* dry,
+        int32_t fan_count, int32_t target_count, int32_t frames, float* mix);
+
 #ifdef __cplusplus
 }
 #endif

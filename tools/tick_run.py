@@ -3,12 +3,20 @@
 every source of a config's frame (fans x targets) spatialized from the frame's own result blocks,
 `frames` samples per buffer at 48 kHz. GPU box only.
     python3 tools/tick_run.py [config] [steps] [--frames N]
+    python3 tools/tick_run.py --mix-batch FANS [steps] [--frames N] [--targets T]
 Per tick, on torch's stream:
   (a) device tick   art_launch_device + art_dsp_tick_device (no host synchronisation)
   (b) host params   art_launch_device, D2H copy of the settings sections (pinned), art_dsp_tick_params_host,
                     H2D copy of the parameters (pinned), art_dsp_process_device: the path (a) replaces
+  (c) listener mix  art_launch_device + art_dsp_tick_mix_device: one dry buffer per target in, one mix
+                    per fan out. Before timing, (c)'s mix is compared with an ordered sum over (a)'s wet
+                    buffers. (a+) is the path (c) replaces: (a) with a torch broadcast of the dry input
+                    in front and a torch sum of the wet buffers behind it
 and the parameter step alone (art_dsp_tick_params_device back to back: an upper bound of
-dsp_tick_params_kernel's own time; a rocprofv3 --kernel-trace of this tool gives the kernel's)."""
+dsp_tick_params_kernel's own time; a rocprofv3 --kernel-trace of this tool gives the kernel's).
+--mix-batch times art_dsp_mix_device alone (device events) on FANS fans of random sources beside
+art_dsp_process_device on the same FANS * T sources, and prints the algorithmic HBM bytes of both
+(a rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass of this mode gives the measured ones)."""
 import ctypes as C
 import os
 import sys
@@ -39,13 +47,88 @@ def timed(one, steps, what, cfg):
     return ms
 
 
+def take(argv, flag, default):
+    if flag not in argv:
+        return default
+    at = argv.index(flag)
+    v = int(argv[at + 1])
+    del argv[at:at + 2]
+    return v
+
+
+def ordered_sum(wet, S, T):
+    """float32 [S*T, n] -> [S, n]: one add per target in ascending order, from the first buffer itself."""
+    wet = wet.reshape(S, T, -1)
+    acc = wet[:, 0].copy()
+    for t in range(1, T):
+        acc = np.add(acc, wet[:, t], dtype=np.float32)
+    return acc
+
+
+def mix_batch(F, T, frames, steps):
+    """art_dsp_mix_device on F fans x T targets beside art_dsp_process_device on the same F*T sources."""
+    from art.dsp import AudioSource
+    rng = np.random.default_rng(12)
+    n = F * T
+    st = SpatializerSettings()
+    base = []
+    for k in range(64):  # 64 parameter records of every filter class, repeated over the batch
+        d = rng.standard_normal(3)
+        d /= np.linalg.norm(d)
+        src = AudioSource(data=np.zeros(2, np.float32), muffle_strength=float(rng.choice([0.0, rng.random()])),
+                          reverb_volume=float(rng.random()), local_dir=tuple(float(v) for v in d),
+                          listener_distance=float(rng.uniform(0, 30)), volume_multiplier=float(rng.uniform(0.5, 1.0)))
+        base.append(art.dsp.source_params(st, src, SAMPLE_RATE))
+    params = np.concatenate(base)[rng.integers(0, 64, n)]
+    dev = torch.device("cuda", 0)
+    ctx = art.Context(1)
+    d_par = torch.from_numpy(params.view(np.uint8).copy()).to(dev)
+    dry = (rng.standard_normal((T, frames * 2)) * 0.5).astype(np.float32)
+    d_dry = torch.from_numpy(dry).to(dev)
+    d_mix = torch.zeros((F, frames * 2), dtype=torch.float32, device=dev)
+    d_state = torch.zeros(n * 32, dtype=torch.uint8, device=dev)
+    sp = torch.cuda.current_stream().cuda_stream
+    print(f"mix batch: {F} fans x {T} targets = {n} sources, {frames} frames", flush=True)
+    alg_mix = 8 * T * frames + 8 * F * frames + 96 * F * T
+    alg_unmixed = 16 * n * frames + 96 * n
+    print(f"mix batch: algorithmic HBM bytes: art_dsp_mix_device {alg_mix} (8 T frames + 8 F frames + 96 F T), "
+          f"art_dsp_process_device {alg_unmixed} (16 n frames + 96 n)", flush=True)
+
+    def ev_time(one, what):
+        for _ in range(3):
+            one()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            one()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+        ts.sort()
+        print(f"mix batch: {what}: min {ts[0]:.1f} us, median {ts[len(ts) // 2]:.1f} us over {steps} calls "
+              f"(device events around one call)", flush=True)
+
+    ev_time(lambda: art.dsp.mix_device(ctx, d_dry, d_par, d_state, F, T, frames, d_mix, sp), "art_dsp_mix_device")
+    if n * frames * 8 < 0x7fffffff:
+        d_data = d_dry.repeat(F, 1)
+        lib = ctx.lib
+
+        def unmixed():
+            rc = lib.art_dsp_process_device(ctx.ptr, d_data.data_ptr(), d_par.data_ptr(), d_state.data_ptr(), n, frames, sp)
+            assert rc == 0, rc
+        ev_time(unmixed, "art_dsp_process_device, same sources")
+    ctx.close()
+
+
 def main():
     argv = sys.argv[1:]
-    frames = 1024
-    if "--frames" in argv:
-        at = argv.index("--frames")
-        frames = int(argv[at + 1])
-        del argv[at:at + 2]
+    frames = take(argv, "--frames", 1024)
+    targets = take(argv, "--targets", 4)
+    batch = take(argv, "--mix-batch", 0)
+    if batch:
+        return mix_batch(batch, targets, frames, int(argv[0]) if argv else 20)
     cfg = art.CONFIGS[int(argv[0]) if len(argv) > 0 else 2]
     steps = int(argv[1]) if len(argv) > 1 else 500
     scene, org, params = art.synth(cfg)
@@ -99,6 +182,23 @@ def main():
         rc = lib.art_dsp_process_device(ctx.ptr, d_data.data_ptr(), d_par.data_ptr(), d_state.data_ptr(), n, frames, sp)
         assert rc == 0, rc
 
+    # (c): one dry buffer per target, one mix per fan; (a+): the same through (a)'s interface
+    dry = (rng.standard_normal((T, frames * 2)) * 0.5).astype(np.float32)
+    d_dry = torch.from_numpy(dry).to(dev)
+    d_mix = torch.zeros((S, frames * 2), dtype=torch.float32, device=dev)
+    d_mix_t = torch.zeros((S, frames * 2), dtype=torch.float32, device=dev)
+    d_state_c = torch.zeros(n * 32, dtype=torch.uint8, device=dev)
+    d_par_c = torch.zeros(n * 32, dtype=torch.uint8, device=dev)
+
+    def tick_c(i):
+        ctx.launch_device(d_org.data_ptr(), S, d_blk.data_ptr(), 0, sp)
+        art.dsp.tick_mix_device(ctx, d_blk, S, d_ls, d_dry, d_state_c, frames, d_par_c, d_mix, None, 0, sp)
+
+    def tick_a_plus(i):
+        d_data.view(S, T, frames * 2).copy_(d_dry.unsqueeze(0).expand(S, T, frames * 2))
+        tick_a(i)
+        torch.sum(d_data.view(S, T, frames * 2), dim=1, out=d_mix_t)
+
     def params_only(i):
         art.dsp.tick_params_device(ctx, d_blk, S, d_ls, d_par, None, 0, sp)
 
@@ -114,12 +214,27 @@ def main():
     same = bool((d_par.cpu().numpy() == host_par).all())
     print(f"config {cfg.index}: device parameters equal the host twin's: {same}", flush=True)
 
+    # (c)'s mix equals the ordered sum over (a)'s wet buffers, from equal (zero) states
+    keep = d_data.clone()
+    d_data.view(S, T, frames * 2).copy_(d_dry.unsqueeze(0).expand(S, T, frames * 2))
+    d_state.zero_()
+    d_state_c.zero_()
+    tick_a(0)
+    tick_c(0)
+    torch.cuda.synchronize()
+    want = ordered_sum(d_data.cpu().numpy(), S, T)
+    same_mix = d_mix.cpu().numpy().tobytes() == want.tobytes() and bool((d_state.cpu() == d_state_c.cpu()).all())
+    print(f"config {cfg.index}: (c)'s mix and state equal the ordered sum over (a)'s wet buffers: {same_mix}", flush=True)
+    d_data.copy_(keep)
+
     t_f = timed(frame_only, steps, "art_launch_device alone", cfg)
     t_a = timed(tick_a, steps, "(a) art_launch_device + art_dsp_tick_device", cfg)
     t_b = timed(tick_b, steps, "(b) art_launch_device + D2H settings + host params + H2D + art_dsp_process_device", cfg)
+    t_c = timed(tick_c, steps, "(c) art_launch_device + art_dsp_tick_mix_device", cfg)
+    t_ap = timed(tick_a_plus, steps, "(a+) torch broadcast of the dry input + (a) + torch sum of the wet buffers", cfg)
     t_p = timed(params_only, steps, "art_dsp_tick_params_device alone, back to back", cfg)
-    print(f"config {cfg.index}: tick_a_ms {t_a:.4f} tick_b_ms {t_b:.4f} frame_ms {t_f:.4f} params_step_ms {t_p:.4f} "
-          f"a_over_b {t_a / t_b:.3f}", flush=True)
+    print(f"config {cfg.index}: tick_a_ms {t_a:.4f} tick_b_ms {t_b:.4f} tick_c_ms {t_c:.4f} tick_a_plus_ms {t_ap:.4f} "
+          f"frame_ms {t_f:.4f} params_step_ms {t_p:.4f} a_over_b {t_a / t_b:.3f} c_over_a {t_c / t_a:.3f}", flush=True)
     ctx.close()
 
 
