@@ -698,6 +698,11 @@ __device__ __forceinline__ void winner_of(const DevScene& sc, const Seg& s, int 
 // list: a finished ray's quad only helps the others through work sharing), and the echo segments and
 // hit records go to fixed per-bounce slots (VisPairs::fixed): no path launch and no reservation
 // atomics per bounce.
+// ONE (the one-hit fused plan, any non-FOLD bounce-0 cast): the same record at the ray's slot and
+// nothing else of the path: the echo slot takes the provisional echo half (0 for a miss; an echo
+// wave that finds a blocker stores the reset 0 over it), and a slot without a hit marks its hit
+// record too (hrec.w = kNoRecord), so a muffle wave reads the hit records alone.
+template <bool ONE = false>
 __device__ __forceinline__ void fold_path(const DevScene& sc, const FrameParams& fp, const FanLayout& L, uint8_t* block,
                                           const float* origins, const VisPairs& vp, float4* state, int step, uint32_t sidx,
                                           int fan, int ray,
@@ -719,13 +724,20 @@ __device__ __forceinline__ void fold_path(const DevScene& sc, const FrameParams&
     if (hit) {   // (the echo's index is ray * H + hits - 1 = ray * H + step: every earlier bounce hit)
       const vec3 off = o - d * kEps;                 // :124, :158
       const float dist0 = distance(O, o);            // :130 (un-offset hit point)
-      vp.out[rec] = make_uint2(__float_as_uint(dist0), f32tof16(dist0 * echo_of(sc, type, idx)));  // :142-144
+      const uint32_t half = f32tof16(dist0 * echo_of(sc, type, idx));  // :142-144
+      vp.out[rec] = make_uint2(__float_as_uint(dist0), half);
       vp.hrec[rec] = make_float4(off.x, off.y, off.z, __uint_as_float((uint32_t)fan * (uint32_t)fp.T));  // batch slot 0
-      echo[ray * H + hits - 1] = 0;  // a blocked echo keeps the reset value (:76); the echo traversal stores the rest
+      // FOLD: a blocked echo keeps the reset value (:76); the echo traversal stores the rest
+      echo[ray * H + hits - 1] = ONE ? (uint16_t)half : (uint16_t)0;
     } else {
       vp.out[rec] = make_uint2(0u, kNoRecord);
+      if (ONE) {
+        vp.hrec[rec] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kNoRecord));
+        if (slot_ok) echo[ray] = 0;  // a miss keeps the reset value (:76, :200-207)
+      }
     }
   }
+  if (ONE) return;
   // termination / reflection (:179-193, ReflectRay :456-532)
   bool next = hit;  // a miss ends the ray (:200-207)
   if (hit) next = (hits >= H || life <= 0.0f) ? false : reflect_at_hit(sc, fp, type, idx, o, d, life);
@@ -841,7 +853,10 @@ __global__ __launch_bounds__(TAB ? 1024 : 256) __attribute__((amdgpu_waves_per_e
   quad_nearest_core<EX, OBB, false, TAB, LOG>(sc, make_seg(o, d), alive, lane, my, s_bound + 16 * w, s_key + 16 * w, best,
                                               code, ex, TAB ? reinterpret_cast<const NodeTab*>(&s_tab) : nullptr,
                                               s_log + 256 * (LOG ? w : 0), s_lcnt + 16 * (LOG ? w : 0));
-  if (FOLD) {
+  // The one-hit fused plan (vp.fixed set on a non-FOLD cast, bounce 0 only): the ray's hit record and
+  // provisional echo half from this epilogue (fold_path<true>), no nearest-hit store.
+  const bool one = !FOLD && vp.fixed != 0u;  // (kernel-uniform)
+  if (FOLD || one) {
     // The ray's state is fetched again rather than kept live across the traversal (a memory
     // clobber: the compiler may not reuse the values loaded before it): 64 VGPRs, no spills.
     asm volatile("" ::: "memory");
@@ -852,7 +867,7 @@ __global__ __launch_bounds__(TAB ? 1024 : 256) __attribute__((amdgpu_waves_per_e
       slot_ok = sl < fp.R;
       ray = slot_ok ? ray_order[sl] : 0;
       out = (uint32_t)g * 64u + (uint32_t)rr2;
-      if (step == 0) {
+      if (!FOLD || step == 0) {
         o = load3(origins, fan);
         d = load_dir(sc.dirs, ray);
         life = fp.max_life;
@@ -867,36 +882,39 @@ __global__ __launch_bounds__(TAB ? 1024 : 256) __attribute__((amdgpu_waves_per_e
         alive = slot_ok && ((__float_as_int(b.w) >> 8) & 1) != 0;
       }
     }
-    if (EX) exec_add(fp.exec, kExecEchoPairs, (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(alive && code != kNoHit) & kQuad0));
-    fold_path(sc, fp, L, block, origins, vp, state, step, out, fan, ray, slot_ok, o, d, life, nhits, alive, best, code,
-              (lane & 3) == 0);
-    return;
-  }
-  // (the ray slot stays a 32-bit value across the traversal: an opaque copy keeps the compiler from
-  // widening it to a 64-bit offset before the loop, two more live VGPRs)
-  asm volatile("" : "+v"(out));
-  if ((lane & 3) == 0 && write) hits[out] = make_int2(__float_as_int(best), code);
-  if constexpr (LOG) {
-    // The ray's record: its leaves, or kLogTraverse for a ray the replay may not decide. The ray is
-    // fetched again rather than kept live across the traversal (as FOLD does above).
-    asm volatile("" ::: "memory");
-    const int qd = lane & 3, rq = 16 * w + (lane >> 2);  // the workgroup's ray
-    const int fan2 = g / nrb, sl = (g - fan2 * nrb) * 64 + rr;
-    const vec3 O = load3(origins, fan2), dd = load_dir(sc.dirs, sl < fp.R ? ray_order[sl] : 0);
-    const float d1 = fabsf(dd.x) + fabsf(dd.y) + fabsf(dd.z);
-    bool trav = true;
-    uint32_t cnt = 0u;
-    if (sc.bvh_levels > 0) {
-      float xcap;
-      const float om = log_margin_om(sc, O, d1, xcap);  // the cast's own operand, so the same forced rays
-      cnt = (uint32_t)s_lcnt[rq];
-      Seg sd;  // (force_all reads the direction only)
-      sd.o = O; sd.d = sd.inv = dd; sd.a2 = 0.0f;
-      trav = force_all(sd, om) || cnt > (uint32_t)kLogK || !(best * d1 <= xcap);
+    if (FOLD) {
+      if (EX) exec_add(fp.exec, kExecEchoPairs, (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(alive && code != kNoHit) & kQuad0));
+      fold_path(sc, fp, L, block, origins, vp, state, step, out, fan, ray, slot_ok, o, d, life, nhits, alive, best, code,
+                (lane & 3) == 0);
+      return;
     }
-    uint2 v = reinterpret_cast<const uint2*>(s_log)[rq * 4 + qd];
-    if (qd == 0) v.x = (v.x & 0xffff0000u) | (trav ? kLogTraverse : cnt);
-    if (write) reinterpret_cast<uint2*>(el.rec)[(size_t)out * 4 + qd] = v;
+    if constexpr (LOG) {
+      // The ray's record: its leaves, or kLogTraverse for a ray the replay may not decide, from the
+      // ray fetched again above (the logging cast runs in the fused plan only).
+      const int qd = lane & 3, rq = 16 * w + (lane >> 2);  // the workgroup's ray
+      const vec3 O = o, dd = d;
+      const float d1 = fabsf(dd.x) + fabsf(dd.y) + fabsf(dd.z);
+      bool trav = true;
+      uint32_t cnt = 0u;
+      if (sc.bvh_levels > 0) {
+        float xcap;
+        const float om = log_margin_om(sc, O, d1, xcap);  // the cast's own operand, so the same forced rays
+        cnt = (uint32_t)s_lcnt[rq];
+        Seg sd;  // (force_all reads the direction only)
+        sd.o = O; sd.d = sd.inv = dd; sd.a2 = 0.0f;
+        trav = force_all(sd, om) || cnt > (uint32_t)kLogK || !(best * d1 <= xcap);
+      }
+      uint2 v = reinterpret_cast<const uint2*>(s_log)[rq * 4 + qd];
+      if (qd == 0) v.x = (v.x & 0xffff0000u) | (trav ? kLogTraverse : cnt);
+      if (write) reinterpret_cast<uint2*>(el.rec)[(size_t)out * 4 + qd] = v;
+    }
+    fold_path<true>(sc, fp, L, block, origins, vp, nullptr, 0, out, fan, ray, slot_ok, o, d, life, 0, alive, best, code,
+                    (lane & 3) == 0);
+  } else {
+    // (the ray slot stays a 32-bit value across the traversal: an opaque copy keeps the compiler from
+    // widening it to a 64-bit offset before the loop, two more live VGPRs)
+    asm volatile("" : "+v"(out));
+    if ((lane & 3) == 0 && write) hits[out] = make_int2(__float_as_int(best), code);
   }
 #ifdef ART_DIAG
   if (lane == 0) diag_add(0, clock64() - t0);
@@ -1129,19 +1147,19 @@ __global__ __launch_bounds__(64 * kPathWaves) __attribute__((amdgpu_waves_per_eu
 // blocked (wave-uniform mask), which ends every traversal of that segment. Any-hit is an OR over
 // the subtrees, so the split does not change a verdict.
 // ------------------------------------------------------------------------------------------
-// One-hit frames with one batch slot (H == 1, TC == 1) trace the echo rays straight from the
+// One-hit frames with one batch slot and hit outputs (H == 1, TC == 1) trace the echo rays straight from the
 // nearest hits (HM: `blk` = a 64-ray group), so the traversal does not wait for the path kernel:
 // the segment, its output index and value are the path kernel's own expressions (:111, :124-145,
 // the zero-distance re-evaluation included), and the traversal stores the echo half or, when a
 // collider blocks it, the reset value 0 (the path kernel, running beside it, then leaves those
-// slots alone). With H == 1 no later batch resets a ray's slot, so every hit slot is live.
+// slots alone). With H == 1 no later batch resets a ray's slot, so every hit slot is live. (Without hit
+// outputs the fused plan runs instead, from the cast's hit records: vis_quad_body's ONE.)
 struct EchoFromHits {
   FrameParams fp;
   FanLayout L;
   const float* origins;
   const int* ray_order;
   const int2* pre;
-  int no_path;  // the frame runs no path kernel: the echo traversal writes the misses' reset 0 and counts the echo rays
 };
 // The hit of ray slot r of 64-ray group g from its nearest-hit record, as path_kernel computes it
 // (:111, :124, the zero-distance re-evaluation included): false for a slot past the fan's rays
@@ -1316,19 +1334,32 @@ __device__ __forceinline__ bool quad_echo_core(const DevScene& sc, Seg s, float 
   return !((wblocked >> wq) & 1u);
 }
 
-// REPLAY (HM, echo_muffle_kernel's non-counting OBB-free instantiation): a quad whose ray has a leaf record
+// ART_REPLAY_DEAL 1: the replayed leaf tests of the wave's 16 rays are dealt evenly over its 16
+// quads (quad q tests items q, q + 16, ... of the flattened (ray, leaf) list, segment and maxd of the
+// item's ray from LDS): ceil(sum n / 16) steps instead of max n, no early exit. A verdict is an OR
+// over a ray's leaves, so the order changes no result. s_deal: 16 segments (3 float4) and the item
+// list (16 * kLogK u32) in LDS. 0: each quad tests its own record, to its first blocker.
+// Measured: config 2 0.0940 -> 0.0905 ms/step with the dealing on.
+#ifndef ART_REPLAY_DEAL
+#define ART_REPLAY_DEAL 1
+#endif
+constexpr int kDealWords = 16 * 12 + 16 * kLogK;
+// REPLAY (ONE, echo_muffle_kernel's non-counting OBB-free instantiation): a quad whose ray has a leaf record
 // (EchoLog, el.rec set: the nearest cast logged this frame) tests the record's leaves against the
 // echo segment, 4 slots per step, to its first blocker; the rays marked kLogTraverse run
 // quad_echo_core in the same wave, where the replaying quads are idle quads that share their work.
 // s_rec: the wave's 16 records in LDS.
-template <bool OBB, bool HM, bool REPLAY = false>
+// ONE (echo_muffle_kernel): the one-hit fused plan's records at fixed slots (fold_path<true>); the cast
+// stored each hit's echo half already, so a quad stores only a blocked echo's reset 0.
+template <bool OBB, bool HM, bool REPLAY = false, bool ONE = false>
 __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs& vp, const uint32_t* count,
                                               unsigned long long* ex, uint32_t blk, int w, uint32_t* s_wave,
                                               const uint32_t* ecnt, int bounce, uint8_t* block, const EchoFromHits& eh,
-                                              const EchoLog* el = nullptr, uint16_t* s_rec = nullptr) {
+                                              const EchoLog* el = nullptr, uint16_t* s_rec = nullptr,
+                                              uint32_t* s_deal = nullptr) {
   const int lane = threadIdx.x & 63, qd = lane & 3;
   const int wq = lane >> 2, slot = w * 16 + wq;                // segment of the block's 64-pair batch
-  if (sc.bvh_levels == 0 && !HM) return;                       // no colliders: nothing blocks
+  if (sc.bvh_levels == 0 && !HM) return;                       // no colliders: nothing blocks (ONE: and no echo ray to count)
   bool valid;
   uint32_t p = 0u, out_at = 0u;
   uint16_t out_val = 0;
@@ -1344,29 +1375,31 @@ __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs
   if (HM) {
     bool slot_ok;
     valid = echo_seg_from_hit(sc, eh, blk, slot, s, maxd, out_at, out_val, slot_ok);
-    if (eh.no_path) {  // the path kernel's duties for this frame: a miss keeps the reset 0 (:76, :200-207)
-      if (slot_ok && !valid && qd == 0) reinterpret_cast<uint16_t*>(block)[out_at] = 0;
-      if (ex) exec_add(ex, kExecEchoPairs, (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(valid) & kQuad0));
-    }
     if (!__any(valid)) return;
   } else {
-    if (vp.fixed) {  // bounce `bounce`'s compact records at fixed slots: 64-slot group blk (fold_path)
-      p = (uint32_t)bounce * vp.fixed + blk * 64u + (uint32_t)slot;
+    if (ONE || vp.fixed) {  // bounce `bounce`'s compact records at fixed slots: 64-slot group blk (fold_path)
+      p = (ONE ? 0u : (uint32_t)bounce * vp.fixed) + blk * 64u + (uint32_t)slot;
       const uint2 ov = vp.out[p];
+      float4 hr = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (ONE) hr = vp.hrec[p];  // (beside the marker, not after it: a slot without a hit holds its own marker)
       valid = ov.y != kNoRecord;
+      // (the fused plan runs no path kernel: the echo rays are counted here)
+      if (ONE && ex) exec_add(ex, kExecEchoPairs, (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(valid) & kQuad0));
       if (!__any(valid)) return;
       if (valid) {  // the segment as fold_path's reference expressions give it: off -> fan origin (:124-130)
         const FrameParams& fp = eh.fp;
         const int nrb = (fp.R + 63) >> 6;
         const int fan = (int)(blk / (uint32_t)nrb);
-        const int ray = eh.ray_order[(int)(blk - (uint32_t)fan * nrb) * 64 + slot];
-        const float4 hr = vp.hrec[p];
+        if (!ONE) hr = vp.hrec[p];
         const vec3 off = mk3(hr.x, hr.y, hr.z), O = load3(eh.origins, fan);
         s = make_seg(off, normalize(O - off));
         maxd = __uint_as_float(ov.x);
         owner = kNoOwner;
-        out_at = (uint32_t)(((size_t)fan * eh.L.stride + eh.L.echo_off) / 2) + (uint32_t)(ray * fp.H + bounce);
-        out_val = (uint16_t)(ov.y & 0xffffu);
+        if (!ONE) {
+          const int ray = eh.ray_order[(int)(blk - (uint32_t)fan * nrb) * 64 + slot];
+          out_at = (uint32_t)(((size_t)fan * eh.L.stride + eh.L.echo_off) / 2) + (uint32_t)(ray * fp.H + bounce);
+          out_val = (uint16_t)(ov.y & 0xffffu);
+        }
       }
     } else {
       // all echo pairs, or (bounce >= 0) those bounce `bounce` emitted: they follow the earlier bounces'
@@ -1396,6 +1429,56 @@ __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs
       replayed = valid && n <= (uint32_t)kLogK;  // (kLogTraverse: the echo traversal below)
       const BvhRes br = bvh_res(sc);
       const int qshift = lane & ~3;
+#if ART_REPLAY_DEAL
+      float4* const s_seg = reinterpret_cast<float4*>(s_deal);  // [16][3]: (o, maxd), (d, a2), (1/d, owner)
+      uint32_t* const s_item = s_deal + 16 * 12;                // ray << 16 | leaf id, the rays' leaves back to back
+      const uint32_t nq = replayed ? n : 0u;
+      uint32_t inc = nq;  // inclusive prefix sums of the quads' leaf counts (a quad's lanes agree)
+      for (int sft = 4; sft < 64; sft <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)inc, sft);
+        if (lane >= sft) inc += up;
+      }
+      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63), start = inc - nq;
+      if (qd == 0) s_seg[wq * 3] = make_float4(s.o.x, s.o.y, s.o.z, maxd);
+      if (qd == 1) s_seg[wq * 3 + 1] = make_float4(s.d.x, s.d.y, s.d.z, s.a2);
+      if (qd == 2) s_seg[wq * 3 + 2] = make_float4(s.inv.x, s.inv.y, s.inv.z, __int_as_float(owner));
+      for (uint32_t j = (uint32_t)qd; j < nq; j += 4u) s_item[start + j] = ((uint32_t)wq << 16) | s_rec[wq * 16 + 1 + j];
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      // item k's leaf slot of this lane (32 B: OBB-free scenes), fetched one step ahead of its test
+      auto fetch = [&](uint32_t k, uint32_t& ray, float4& qa, float4& qb) {
+        const uint32_t it = s_item[k];
+        ray = it >> 16;
+        const int at = ((int)(it & 0xffffu) * kBvhLeaf + qd) * 32;
+        qa = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(br.leaves, at, 0, 0));
+        qb = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(br.leaves, at + 16, 0, 0));
+      };
+      float4 na = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nb = na;
+      uint32_t nray = 0u, wblk = 0u;  // wblk: wave-uniform mask of the rays found blocked
+      bool on = (uint32_t)wq < total;
+      if (on) fetch((uint32_t)wq, nray, na, nb);
+      for (uint32_t base = 0u; base < total; base += 16u) {  // (wave-uniform)
+        const float4 qa = na, qb = nb;
+        const uint32_t ray = nray;
+        const bool more = base + 16u + (uint32_t)wq < total;
+        if (more) fetch(base + 16u + (uint32_t)wq, nray, na, nb);
+        bool blk_here = false;
+        if (on) {
+          const float4 a = s_seg[ray * 3u], b = s_seg[ray * 3u + 1u], c = s_seg[ray * 3u + 2u];
+          Seg sr;
+          sr.o = mk3(a.x, a.y, a.z); sr.d = mk3(b.x, b.y, b.z); sr.inv = mk3(c.x, c.y, c.z); sr.a2 = b.w;
+          int tid;
+          float d;
+          const bool hh = leaf_rec_test(sr, qa, qb, d, tid, nt);
+          blk_here = hh && d < a.w && tid != __float_as_int(c.w);  // :373-394, quad_echo_core's test
+        }
+        const bool hit_quad = ((uint32_t)(__builtin_amdgcn_ballot_w64(blk_here) >> qshift) & 0xFu) != 0u;
+        for (unsigned long long bq = __builtin_amdgcn_ballot_w64(hit_quad) & kQuad0; bq; bq &= bq - 1ull)
+          wblk |= 1u << __builtin_amdgcn_readlane((int)ray, __builtin_ctzll(bq));
+        on = more;
+      }
+      blocked = ((wblk >> wq) & 1u) != 0u;
+#else
       // leaf j's slot of this lane (32 B: OBB-free scenes), fetched one step ahead of its test
       auto fetch = [&](uint32_t j, float4& qa, float4& qb) {
         const int at = ((int)s_rec[wq * 16 + 1 + j] * kBvhLeaf + qd) * 32;
@@ -1419,6 +1502,7 @@ __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs
         blocked = blocked || ((uint32_t)(__builtin_amdgcn_ballot_w64(blk_here) >> qshift) & 0xFu) != 0u;
         on = more && !blocked;
       }
+#endif
     }
     if (el->count) {
       const uint32_t nr = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(replayed) & kQuad0);
@@ -1426,10 +1510,18 @@ __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs
       if (lane == 0) atomicAdd(el->count + (blockIdx.x & (kEchoCountSlots - 1)), (unsigned long long)nr | ((unsigned long long)nv << 32));
     }
   }
-  bool visible = quad_echo_core<OBB, HM && ART_ECHO_PARK>(sc, s, maxd, owner, valid && !replayed, lane, s_wave, nt, nnode);
+  bool visible = quad_echo_core<OBB, (HM || ONE) && ART_ECHO_PARK>(sc, s, maxd, owner, valid && !replayed, lane, s_wave, nt, nnode);
   if (REPLAY && replayed) visible = !blocked;
   if (HM) {
     if (valid && qd == 0) reinterpret_cast<uint16_t*>(block)[out_at] = visible ? out_val : (uint16_t)0;  // :76, :142-144
+  } else if (ONE) {
+    if (valid && !visible && qd == 0) {  // a blocked echo: the reset value over the cast's provisional half (:76)
+      const FrameParams& fp = eh.fp;
+      const int nrb = (fp.R + 63) >> 6;
+      const int fan = (int)(blk / (uint32_t)nrb);
+      const int ray = eh.ray_order[(int)(blk - (uint32_t)fan * nrb) * 64 + slot];
+      reinterpret_cast<uint16_t*>(block)[(uint32_t)(((size_t)fan * eh.L.stride + eh.L.echo_off) / 2) + (uint32_t)ray] = 0;
+    }
   } else if (vp.fixed) {
     if (valid && visible && qd == 0) reinterpret_cast<uint16_t*>(block)[out_at] = out_val;  // :142-144
   } else if (valid && visible && qd == 0) {  // visible: the echo is stored (:142-144)
@@ -1685,9 +1777,9 @@ __device__ __forceinline__ bool muffle_blocked(const DevScene& sc, vec3 off, vec
   return blocked;
 }
 
-// HM: one-hit frames with one batch slot whose path kernel does not run: lane i is ray slot i
-// (64-ray group i / 64) and its muffle rays start from the nearest hit as the path kernel computes
-// it (hit_from_pre); the accumulator base is fan * T (TC == 1: batch slot 0).
+// HM: one-hit frames with one batch slot whose path kernel does not run (the fused plan): lane i is
+// ray slot i (64-ray group i / 64) and its muffle rays start from the hit record the cast's epilogue
+// stored there (fold_path<true>: off and the accumulator base fan * T; TC == 1: batch slot 0).
 // i = this lane's hit record / ray slot (i - lane wave-uniform); targets by, by + gy, ...
 template <bool EX, bool OBB, bool HM>
 __device__ __forceinline__ void muffle_body(const DevScene& sc, const FrameParams& fp, const VisPairs& vp,
@@ -1700,17 +1792,12 @@ __device__ __forceinline__ void muffle_body(const DevScene& sc, const FrameParam
   bool valid = i < n;
   vec3 off = mk3(0.0f, 0.0f, 0.0f);
   uint32_t dbase = 0u;
-  if (HM) {
-    bool slot_ok;
-    int fan = 0, ray = 0, type = kNone, idx = 0;
-    vec3 O, o;
-    valid = valid && hit_from_pre(sc, eh, i >> 6, (int)(i & 63u), slot_ok, fan, ray, O, o, off, type, idx);
-    dbase = (uint32_t)fan * (uint32_t)fp.T;
-  } else {
+  {
     // (compact records: fold_path; the hit record is fetched beside the marker, not after it: a
-    // slot without a record holds a stale one, never used)
+    // slot without a record holds a stale one, never used. HM: fold_path<true> marks the hit record
+    // of a slot without a hit itself, one load per lane)
     const float4 r = vp.hrec[i < n ? i : 0u];
-    if (vp.fixed) valid = valid && vp.out[i].y != kNoRecord;
+    if (!HM && vp.fixed) valid = valid && vp.out[i].y != kNoRecord;
     off = mk3(r.x, r.y, r.z);
     dbase = __float_as_uint(r.w);
     valid = valid && dbase != kNoRecord;
@@ -1752,7 +1839,7 @@ __device__ __forceinline__ void muffle_body(const DevScene& sc, const FrameParam
 // the uneven work per target left XCDs idle (config 5: 171 -> 193 us), so it keeps the plain order.
 // Any other shape keeps the plain (b % M, b / M) order. Round 6 (ART_MUFFLE_XCD 2, the default
 // when the group count is a multiple of 8): each muffle wave runs on the XCD that traced its 64-ray
-// group's echoes (echo_muffle_kernel), so a group's nearest hits are read from that XCD's L2 and
+// group's echoes (echo_muffle_kernel), so a group's hit records are read from that XCD's L2 and
 // each L2 holds every target's lists: echo+muffle config 4 594.5 -> 585.7 us, config 3 88.5 ->
 // 87.4, config 2 54.2 -> 53.6 (HBM bytes per launch at config 4 73.3 -> 75.1 MB: the time is not
 // set by the traffic).
@@ -1781,8 +1868,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EX && OBB ?
   muffle_body<EX, OBB, HM>(sc, fp, vp, count, acc, eh, blockIdx.x * 256u + threadIdx.x, (int)blockIdx.y, (int)gridDim.y);
 }
 
-// One-hit frames with one batch slot and no path kernel (HM2): the echo traversal and the muffle
-// rays, both from the nearest hits, as one launch on the launch stream: workgroups [0, 4 groups) are
+// One-hit frames with one batch slot and no path kernel (the fused plan): the echo traversal and the muffle
+// rays, both from the hit records of the cast's epilogue (fold_path<true>), as one launch on the launch stream: workgroups [0, 4 groups) are
 // the echo batches (one wave each) (dispatched first, one round of waves), the rest the muffle blocks (mblocks x
 // mt, filling the echo traversal's tails). No side stream, so no fork / join on the frame's path.
 // With OBB tests the joint kernel runs at 6 waves per SIMD (5 counting), where it needs no spills.
@@ -1790,6 +1877,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EX && OBB ?
 // any single wave slot an echo wave frees (with 4-wave workgroups a CU waited for 4 free slots:
 // config 3 0.1686 -> 0.1660 ms/step, config 4 1.164 -> 1.149, config 2 even); the 4 waves of a
 // group or block stay on one XCD (workgroup b runs on XCD b % 8).
+#ifndef ART_MUFFLE_FIRST
+#define ART_MUFFLE_FIRST 0  // (1: the muffle workgroups are dispatched before the echo workgroups, for A/B runs: config 2 0.0940 -> 0.1062 ms/step)
+#endif
 template <bool EX, bool OBB>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OBB ? (EX ? 5 : ART_ECHO_MUFFLE_OBB_WAVES) : kEchoWaves<EX, OBB>)))
 void echo_muffle_kernel(DevScene sc, FrameParams fp, VisPairs vp, const uint32_t* __restrict__ count,
@@ -1797,8 +1887,12 @@ void echo_muffle_kernel(DevScene sc, FrameParams fp, VisPairs vp, const uint32_t
                         uint32_t groups, uint32_t mblocks, int mt, EchoLog el) {
   __shared__ uint32_t s_stk[16 * kBvhStack];
   __shared__ __attribute__((aligned(8))) uint16_t s_rec[EX || OBB ? 4 : 16 * 16];
-  const uint32_t b = blockIdx.x;
+  __shared__ __attribute__((aligned(16))) uint32_t s_deal[ART_REPLAY_DEAL && !EX && !OBB ? kDealWords : 4];
   const uint32_t ne = 4u * groups;  // echo workgroups
+  // (ART_MUFFLE_FIRST: the muffle workgroups take the first indices; both counts are multiples of 8
+  // whenever the XCD placements below apply, so a workgroup's XCD is the same either way)
+  const uint32_t nm = gridDim.x - ne;
+  const uint32_t b = ART_MUFFLE_FIRST ? (blockIdx.x < nm ? ne + blockIdx.x : blockIdx.x - nm) : blockIdx.x;
   ART_WAVE_TIMER(b < ne ? 1u : 2u);
   // (group or muffle block, wave): a group's 4 waves on one XCD when the counts are multiples of 8,
   // else consecutive
@@ -1817,13 +1911,13 @@ void echo_muffle_kernel(DevScene sc, FrameParams fp, VisPairs vp, const uint32_t
     uint32_t g;
     int w;
     split(b, groups, g, w);
-    vis_quad_body<OBB, true, !EX && !OBB>(sc, vp, count, EX ? ex : nullptr, g, w, s_stk, nullptr, -1, block, eh, &el, s_rec);
+    vis_quad_body<OBB, false, !EX && !OBB, true>(sc, vp, count, EX ? ex : nullptr, g, w, s_stk, nullptr, -1, block, eh, &el, s_rec, s_deal);
     return;
   }
   if (ART_MUFFLE_XCD == 2 && groups % 8u == 0u) {
     // group-local muffle waves (muffle_block's note): the wave of (64-ray group G, target t) runs on the XCD
     // that traced G's echo rays (workgroup index % 8 == G % 8), so each XCD fetches only its own
-    // groups' nearest hits (from its L2) and every target's cell lists
+    // groups' hit records (from its L2) and every target's cell lists
     const uint32_t m = b - ne, x = m & 7u, j = m >> 3;
     const int t = (int)(j % (uint32_t)mt);
     const uint32_t G = (j / (uint32_t)mt) * 8u + x;
@@ -2115,8 +2209,8 @@ static PairBufs pair_bufs(void* base, const FrameParams& fp) {
   PairBufs b{};
   const size_t slots = (size_t)fp.S * ((fp.R + 63) / 64) * 64;
   // (multi-hit frames: room for the fixed per-bounce slots of the folded path, H * slots records)
-  const size_t ecap = std::max(echo_cap_of(fp), fp.H > 1 ? slots * fp.H : 0),
-               hcap = std::max((size_t)fp.S * fp.R * fp.H, fp.H > 1 ? slots * fp.H : 0);
+  // (and for the one-hit fused plan's records at fixed slots: `slots` of them, past S * R when R % 64 != 0)
+  const size_t ecap = std::max(echo_cap_of(fp), slots * fp.H), hcap = std::max((size_t)fp.S * fp.R * fp.H, slots * fp.H);
   uint8_t* p = static_cast<uint8_t*>(base);
   size_t off = 0;
   auto take = [&](size_t bytes) { uint8_t* q = p ? p + off : nullptr; off += align256(bytes); return q; };
@@ -2174,8 +2268,8 @@ uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const F
   const size_t hcap = (size_t)fp.S * fp.R * fp.H;
   uint32_t* ecnt = pb.state ? reinterpret_cast<uint32_t*>(pb.state + 2 * (size_t)groups * 64) + (size_t)groups * 64 + kLiveCounters
                             : nullptr;  // per-bounce echo counts (echo_counts)
-  // One-hit frames with one batch slot trace the echo rays straight from the nearest hits (HM)
-  // when the frame's echo traversal fits the chip in one round of waves (4 per 64-ray group, 8 per
+  // One-hit frames with one batch slot and hit outputs trace the echo rays straight from the nearest
+  // hits (HM) when the frame's echo traversal fits the chip in one round of waves (4 per 64-ray group, 8 per
   // SIMD): a larger one would hold every wave slot and starve the path kernel beside it (config 4:
   // path 30 -> 977 us).
   const bool split = echo.st != nullptr;
@@ -2185,11 +2279,18 @@ uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const F
       n = 256;
     return n > 0 ? n : 256;
   }();
-  const bool hm = split && !multi && fp.TC == 1 && groups <= (unsigned)cus * 8u;
+  const bool hm = split && !multi && fp.TC == 1 && L.has_hits && groups <= (unsigned)cus * 8u;
+  // One-hit frames with one batch slot and no hit outputs (the fused plan): no path kernel at all. The
+  // cast's epilogue stores each ray slot's hit record and echo half (fold_path<true>: the misses'
+  // reset too), and the echo traversal and the muffle rays start from the records as one launch on
+  // st (echo_muffle_kernel), at any frame size (no path kernel is left to starve; config 4 1.684 ->
+  // 1.660 ms/step)
+  const bool fused = split && !multi && fp.TC == 1 && !L.has_hits;
   // Multi-hit frames with one batch slot and no hit outputs fold the path kernel into the nearest
   // kernel (nearest_first_kernel<..., FOLD>): records at fixed per-bounce slots, no live list
   const bool fold = split && multi && fp.TC == 1 && !L.has_hits;
-  pb.vp.fixed = fold ? groups * 64u : 0u;
+  // (the fused plan's records sit at the same fixed slots, bounce 0 only)
+  pb.vp.fixed = fold || fused ? groups * 64u : 0u;
   EchoFromHits eh;
   eh.fp = fp; eh.L = L; eh.origins = origins; eh.ray_order = ray_order; eh.pre = pb.pre;
 #define ART_VIS(S_, BLOCKS_, B_, EX_, OBB_, HM_)                                                                   \
@@ -2200,34 +2301,24 @@ uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const F
     if (fp.exec) { if (obb) ART_VIS(S_, BLOCKS_, B_, true, true, HM_); else ART_VIS(S_, BLOCKS_, B_, true, false, HM_); } \
     else { if (obb) ART_VIS(S_, BLOCKS_, B_, false, true, HM_); else ART_VIS(S_, BLOCKS_, B_, false, false, HM_); }       \
   } while (0)
-  // One-hit frames with one batch slot, no hit outputs (HM2): no path kernel at all; the echo
-  // traversal writes the misses' reset and the muffle kernel starts from the nearest hits too, at
-  // any frame size (no path kernel is left to starve; config 4 1.684 -> 1.660 ms/step)
-  const bool hm2 = split && !multi && fp.TC == 1 && !L.has_hits;
-  // ... and the two as one launch on st (echo_muffle_kernel)
-  const bool fused = hm2;
-  eh.no_path = hm2 ? 1 : 0;
-  const unsigned mblocks = (ART_MEASURE_PARTS == 1 && hm2) ? 0u : hm2 ? (groups + 3) / 4
+  const unsigned mblocks = (ART_MEASURE_PARTS == 1 && fused) ? 0u : fused ? (groups + 3) / 4
                                : (unsigned)(((fold ? (size_t)groups * 64 * fp.H : hcap) + 255) / 256);  // ray slots / hit records
   const unsigned mt = (unsigned)std::min(fp.T, 64);           // targets over the grid (the rest looped)
-#define ART_MUFFLE(S_, EX_, OBB_, HM_)                                                                                  \
-  hipLaunchKernelGGL((muffle_kernel<EX_, OBB_, HM_>), dim3(mblocks, mt), dim3(256), 0, S_, sc, fp, pb.vp, pair_count, \
+  // (the standalone muffle kernel never runs the fused plan's records: HM = false)
+#define ART_MUFFLE(S_, EX_, OBB_)                                                                                       \
+  hipLaunchKernelGGL((muffle_kernel<EX_, OBB_, false>), dim3(mblocks, mt), dim3(256), 0, S_, sc, fp, pb.vp, pair_count, \
                      muffle_acc, eh)
 #define ART_MUFFLE_ANY(S_)                                                                                             \
   do {                                                                                                                 \
-    if (hm2) {                                                                                                         \
-      if (fp.exec) { if (obb) ART_MUFFLE(S_, true, true, true); else ART_MUFFLE(S_, true, false, true); }             \
-      else { if (obb) ART_MUFFLE(S_, false, true, true); else ART_MUFFLE(S_, false, false, true); }                   \
-    } else {                                                                                                           \
-      if (fp.exec) { if (obb) ART_MUFFLE(S_, true, true, false); else ART_MUFFLE(S_, true, false, false); }           \
-      else { if (obb) ART_MUFFLE(S_, false, true, false); else ART_MUFFLE(S_, false, false, false); }                 \
-    }                                                                                                                  \
+    if (fp.exec) { if (obb) ART_MUFFLE(S_, true, true); else ART_MUFFLE(S_, true, false); }                           \
+    else { if (obb) ART_MUFFLE(S_, false, true); else ART_MUFFLE(S_, false, false); }                                 \
   } while (0)
   // Stream plan. Multi-hit frames: per bounce nearest → path on st, that bounce's echo traversal
   // on the side stream right after its path kernel (beside the next bounces' nearest traversals,
   // whose tails leave CUs idle), the muffle kernel after the last bounce on st. One-hit frames
-  // with one batch slot (HM): nearest → echo traversal from the hits on st, path → muffle on the
-  // side stream (the path kernel leaves the critical path). Other one-hit frames: nearest → path →
+  // with one batch slot and hit outputs (HM): nearest → echo traversal from the hits on st, path → muffle on the
+  // side stream (the path kernel leaves the critical path); without hit outputs (fused): nearest →
+  // echo_muffle_kernel on st. Other one-hit frames: nearest → path →
   // echo traversal on st, the muffle kernel on the side stream (the longer kernel stays on st: a
   // fork costs ~10 us before the side stream starts). Without a side stream everything runs on st.
   const bool per_bounce = split && multi && ecnt;
@@ -2279,7 +2370,7 @@ uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const F
     });
 #undef ART_NEAREST
     hipStream_t pst = st;
-    if (hm && !hm2) {  // (HM2 forks the muffle rays below)
+    if (hm) {
       (void)hipEventRecord(echo.fork, st);
       (void)hipStreamWaitEvent(echo.st, echo.fork, 0);
       pst = echo.st;
@@ -2287,7 +2378,7 @@ uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const F
 #define ART_PATH(H_, M_)                                                                                              \
   hipLaunchKernelGGL((path_kernel<H_, M_>), dim3(path_blocks), dim3(64 * kPathWaves), 0, pst, sc, fp, L, origins, block, \
                      ray_order, pb.vp, pair_count, pb.pre, pb.state, k, (int)!hm)
-    if (hm2 || fold) {}
+    if (fused || fold) {}
     else if (L.has_hits) { if (multi) ART_PATH(true, true); else ART_PATH(true, false); }
     else { if (multi) ART_PATH(false, true); else ART_PATH(false, false); }
 #undef ART_PATH
@@ -2310,10 +2401,6 @@ uint32_t launch_raytrace_fast(const DevScene& sc, const FrameParams& fp, const F
     });
 #undef ART_ECHO_MUFFLE
   } else if (hm) {
-    if (hm2) {  // no path kernel: fork the muffle rays here
-      (void)hipEventRecord(echo.fork, st);
-      (void)hipStreamWaitEvent(echo.st, echo.fork, 0);
-    }
     marked(marks, kMarkMuffle, echo.st, [&] { ART_MUFFLE_ANY(echo.st); });  // after the path kernel there
     marked(marks, kMarkEcho, st, [&] { ART_VIS_ANY(st, groups, -1, true); });  // one 64-ray group per workgroup
   } else if (split) {
