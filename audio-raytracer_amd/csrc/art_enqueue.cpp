@@ -100,7 +100,7 @@ int enqueue_kernels(art_ctx* c, Device& dv, const Frame& f, const float* d_origi
   }
   // Everything the stages allocate or create comes first: once the permeation job is forked to the
   // side stream, an early error return would leave it writing the caller's block unjoined.
-  // the permeation job over the BVH (art_trace.hip); reference-order and counting frames sweep every
+  // the permeation job over the BVH (art_permeate.hip); reference-order and counting frames sweep every
   // collider (art_kernels.hip), an independent implementation the parity tests compare too
   const bool perm_bvh = !count && !(c->flags & ART_CTX_FORCE_REFERENCE_ORDER);
   const int chunk = fast_fans_per_launch(f.R, f.H, f.T, f.TC, f.L.stride);

@@ -100,7 +100,7 @@ static void coherent_order(const art_half3* dirs, int R, std::vector<int>& order
 
 // Cube-map direction cells around a target (art_cells.hip): face f = 2 m + (negative), cell (i, j)
 // covers u = v[(m+1)%3] / |v[m]| in [-1 + 2i/G, -1 + 2(i+1)/G] and w = v[(m+2)%3] / |v[m]| likewise
-// (art_trace.hip cube_cell). Each cell's cone: the normalised sum of its corner directions and the
+// (art_trace_muffle.hpp cube_cell). Each cell's cone: the normalised sum of its corner directions and the
 // largest angle to a corner (the farthest point of a convex spherical quadrilateral from an inner
 // point), plus 1e-4 rad for the rounding of the cell lookup and of this float table.
 ConeTable::ConeTable() {

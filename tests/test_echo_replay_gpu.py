@@ -26,7 +26,7 @@ from test_plan_matrix_gpu import check_equal, stale_outputs
 
 pytestmark = pytest.mark.gpu
 
-K_LOG = 15       # kLogK (art_trace.hip): leaf ids a ray's record holds
+K_LOG = 15       # kLogK (art_trace_rays.hpp): leaf ids a ray's record holds
 CAP_FRAC = 0.3   # kLogCapFrac: share of the root box's L1 diagonal that best * |d|_1 may reach
 K_BVH_LEAF = 4   # kBvhLeaf: colliders per leaf
 

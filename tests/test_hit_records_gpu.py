@@ -1,6 +1,6 @@
 """One-hit frames of the fused plan: hit records handed from the bounce-0 cast to the echo and muffle waves.
 
-The cast's epilogue (fold_path<true>, csrc/art_trace.hip) stores for every ray slot of a 64-ray
+The cast's epilogue (fold_path<true>, csrc/art_trace_nearest.hpp) stores for every ray slot of a 64-ray
 group its hit record (echo distance and half, offset hit point, accumulator base) or a no-record
 marker, and the hit's provisional echo half or a miss's 0 in the fan block; the echo waves of
 echo_muffle_kernel start from the records and store only a blocked echo's 0, the muffle waves read

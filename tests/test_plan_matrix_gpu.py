@@ -33,7 +33,7 @@ FUSED, HM, SPLIT, FOLD, PER_BOUNCE = (abi.ART_PLAN_FUSED, abi.ART_PLAN_HM, abi.A
 TAB, OBB, EX, CHUNKED = abi.ART_PLAN_TAB, abi.ART_PLAN_OBB, abi.ART_PLAN_EX, abi.ART_PLAN_CHUNKED
 BASE_PLANS = FUSED | HM | SPLIT | FOLD | PER_BOUNCE
 
-K_TAB_NODES = 1365  # kTabNodes (art_trace.hip): BVH nodes the bounce-0 node table holds
+K_TAB_NODES = 1365  # kTabNodes (art_trace_nearest.hpp): BVH nodes the bounce-0 node table holds
 K_BVH_LEAF = 4      # kBvhLeaf (art_internal.hpp): colliders per BVH leaf
 
 

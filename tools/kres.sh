@@ -1,6 +1,7 @@
 #!/bin/bash
 # Per-kernel VGPRs, spills, occupancy and LDS of one HIP source, as the compiler reports them.
 #   tools/kres.sh [csrc/art_trace.hip] [-DFLAG ...]
+# (the default source holds the raytrace stage; the permeation kernels are a second source, csrc/art_permeate.hip)
 set -euo pipefail
 root=$(cd "$(dirname "$0")/.." && pwd)
 src=${1:-$root/audio-raytracer_amd/csrc/art_trace.hip}; shift || true

@@ -3,7 +3,9 @@
 
   python3 tools/spill_check.py [csrc/art_trace.hip] [-DFLAG ...]
 
-For every kernel: its VGPR count and scratch use, and for each spill slot the stores and reloads
+(The default source holds the raytrace stage; the permeation kernels are a second source, csrc/art_permeate.hip.)
+
+For every kernel: its VGPR count, scratch, LDS, occupancy and code length, and for each spill slot the stores and reloads
 with the loop they sit in (the compiler's "Loop Header" / "in Loop" block annotations). A spill
 stored inside a divergent loop (a narrowed exec mask) and reloaded after it can hand the reloading
 lanes values they never stored; spills outside every loop are read back by the lanes that stored them."""
@@ -36,7 +38,7 @@ for i, line in enumerate(asm):
         else:
             cur["lines"].append(line)
     elif last is not None:  # the resource comments that follow a kernel's code
-        m = re.match(r"^; (NumVgprs|ScratchSize|LDSByteSize): (\d+)", line)
+        m = re.match(r"^; (NumVgprs|ScratchSize|LDSByteSize|Occupancy): (\d+)", line) or re.match(r"^; (codeLenInByte) = (\d+)", line)
         if m:
             last["res"].setdefault(m.group(1), int(m.group(2)))
 
@@ -56,10 +58,10 @@ for k in kernels:
             off = re.search(r"offset:(\d+)", line)
             sites.append((m.group(1), int(off.group(1)) if off else 0, loop))
     name = demangle(k["name"])
-    if k["res"]:  # every kernel: registers, scratch and LDS as the compiler reports them
+    if k["res"]:  # every kernel: registers, scratch, LDS, occupancy and code length as the compiler reports them
         r = k["res"]
         print(f"{name[:160]}: {r.get('NumVgprs', '?')} VGPRs, scratch {r.get('ScratchSize', '?')} B, "
-              f"LDS {r.get('LDSByteSize', '?')} B")
+              f"LDS {r.get('LDSByteSize', '?')} B, occupancy {r.get('Occupancy', '?')}, code {r.get('codeLenInByte', '?')} B")
     if not sites:
         continue
     print(f"{name[:160]}: {len(sites)} scratch ops")
