@@ -142,6 +142,11 @@ class art_target_sync_stats(C.Structure):
                 ("lists_full_rebuild", C.c_int32), ("bytes_uploaded", C.c_uint64)]
 
 
+class art_target_resize_stats(C.Structure):  # ABI 3.7
+    _fields_ = [("kept_bound", C.c_int32), ("added", C.c_int32), ("removed", C.c_int32), ("lists_moved", C.c_int32),
+                ("lists_rebuilt", C.c_int32), ("lists_full_rebuild", C.c_int32), ("bytes_uploaded", C.c_uint64)]
+
+
 class art_exec_kernel(C.Structure):
     _fields_ = [("sphere", C.c_uint64), ("aabb", C.c_uint64), ("obb", C.c_uint64), ("cull_box", C.c_uint64),
                 ("cell_entries", C.c_uint64)]
@@ -267,6 +272,10 @@ SIGNATURES = {
     "art_targets_sync": (I32, [VP]),
     "art_targets_last_sync": (I32, [VP, C.POINTER(art_target_sync_stats)]),
     "art_debug_cells_arena": (I32, [VP, C.POINTER(U64), C.POINTER(U64), C.POINTER(U32)]),
+    "art_targets_reserve": (I32, [VP, I32]),
+    "art_target_capacity": (I32, [VP]),
+    "art_targets_last_resize": (I32, [VP, C.POINTER(art_target_resize_stats)]),
+    "art_debug_target_sync_map": (I32, [VP, VP, I32]),
     "art_device_count": (I32, []),
     "art_create_on": (I32, [C.POINTER(I32), I32, C.POINTER(VP)]),
     # art_synth.h

@@ -81,6 +81,27 @@ class TargetStore:
         self._check(self.ctx.lib.art_targets_last_sync(self.ctx.ptr, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in abi.art_target_sync_stats._fields_}
 
+    def reserve(self, capacity: int):
+        """Room for up to `capacity` targets in scenes bound from now on (art_targets_reserve): a sync
+        whose count stays in [1, capacity] keeps such a scene bound. 0: a count change unbinds."""
+        self._check(self.ctx.lib.art_targets_reserve(self.ctx.ptr, capacity))
+
+    def capacity(self) -> int:
+        return self._check(self.ctx.lib.art_target_capacity(self.ctx.ptr))
+
+    def last_resize(self) -> dict:
+        """What the last sync did to the list and to a bound scene's lists (art_target_resize_stats)."""
+        st = abi.art_target_resize_stats()
+        self._check(self.ctx.lib.art_targets_last_resize(self.ctx.ptr, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in abi.art_target_resize_stats._fields_}
+
+    def sync_map(self) -> np.ndarray:
+        """For each synced index, the synced index the same target held before the last sync (-1: new)."""
+        n = self.synced_count()
+        src = np.full(max(n, 1), -2, np.int32)
+        assert self._check(self.ctx.lib.art_debug_target_sync_map(self.ctx.ptr, src.ctypes.data, n)) == n
+        return src[:n]
+
     def cells_arena(self) -> dict:
         """art_debug_cells_arena of the bound scene (diagnostics, synchronizes)."""
         used, cap, dropped = C.c_uint64(), C.c_uint64(), C.c_uint32()

@@ -47,8 +47,10 @@ namespace {
 // 3.3: art_debug_echo_decided; 3.4: the resident target store (art_target_*, art_targets_*,
 // ART_CTX_RESIDENT_TARGETS, art_debug_cells_arena); 3.5: the audio tick (art_listener,
 // art_dsp_tick_params_host, art_dsp_settings_bind, art_dsp_tick_params_device, art_dsp_tick_device);
-// 3.6: the listener mix (art_dsp_mix_device, art_dsp_tick_mix_device, art_dsp_mix_host)
-constexpr uint32_t kAbiVersion = (3u << 16) | 6u;
+// 3.6: the listener mix (art_dsp_mix_device, art_dsp_tick_mix_device, art_dsp_mix_host); 3.7: targets
+// added and removed on a bound scene (art_targets_reserve, art_target_capacity, art_targets_last_resize,
+// art_debug_target_sync_map)
+constexpr uint32_t kAbiVersion = (3u << 16) | 7u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -341,7 +343,7 @@ ART_API int art_schedule(art_ctx* c, const art_frame_desc* d, const art_fan* fan
   PhaseClock pc(&c->hp);
   Frame& f = c->fr;
   make_frame(d, hits ? ART_OUT_HIT_RESULTS : 0u, f, (c->flags & ART_CTX_RESIDENT_COLLIDERS) ? c->store.synced : nullptr,
-             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0);
+             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0, c->targets.reserved);
   const FanLayout& L = f.L;
   const size_t origins_off = align_up(f.raw_bytes, 16);
   if (!c->h_block.reserve((size_t)fan_count * L.stride)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
@@ -518,14 +520,34 @@ ART_API int art_scene_bind(art_ctx* c, const art_frame_desc* d) {
   if (rc) return rc;
   Frame& f = c->fr;
   make_frame(d, 0u, f, (c->flags & ART_CTX_RESIDENT_COLLIDERS) ? c->store.synced : nullptr,
-             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0);
+             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0, c->targets.reserved);
   if (!c->h_in.reserve(f.raw_bytes)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
   pack_inputs(d, f, static_cast<uint8_t*>(c->h_in.p));
   count_nonowned(c, d);
+  // which target indices own colliders (a count-changing target sync asks; the resident store keeps its own)
+  for (auto& h : c->bind_tid_hist) h.clear();
+  if (f.Tc > 0 && !f.resident) {
+    for (auto& h : c->bind_tid_hist) h.assign(65536, 0);
+    for (int i = 0; i < d->sphere_count; ++i) c->bind_tid_hist[0][(size_t)(d->sphere_colliders[i].audio_target_id + 32768)]++;
+    for (int i = 0; i < d->aabb_count; ++i) c->bind_tid_hist[1][(size_t)(d->aabb_colliders[i].audio_target_id + 32768)]++;
+    for (int i = 0; i < d->obb_count; ++i) c->bind_tid_hist[2][(size_t)(d->obb_colliders[i].audio_target_id + 32768)]++;
+  }
   for (Device& dv : c->devs) {
     rc = upload_scene(c, dv, f, static_cast<const uint8_t*>(c->h_in.p));
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(dv.stream));
+  }
+  if (f.Tc > 0) {
+    // A later target sync allocates nothing: its build selection, and every slot of the pinned
+    // image ring at the largest image Tc targets make ([indices][positions][selection][moves] <=
+    // 24 Tc + 64 bytes). Every earlier sync has completed (the streams were just waited for).
+    const size_t image = 4 * align_up((size_t)f.Tc * 12, 16) + 64;
+    for (HostBuf& b : c->store.h_upd)
+      if (!b.reserve(image)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
+    for (Device& dv : c->devs) {
+      HIP_TRY(c, hipSetDevice(dv.id));
+      if (!dv.tsel.reserve((size_t)kMaxTargets * sizeof(int))) return fail(c, ART_E_NOMEM, "device allocation failed");
+    }
   }
   return ART_OK;
 }

@@ -590,7 +590,8 @@ int launch_build_cells(DevScene& sc, const CellBufs& cb, hipStream_t st) {
   sc.cell_ok = cb.ok;
   sc.cell_cap = cb.cap;
   if (cb.cap == 0) {  // no lists for this scene size (cells_enabled): every target tests every collider
-    if (T > 0 && hipMemsetAsync(cb.ok, 0, (size_t)T * sizeof(uint32_t), st) != hipSuccess) return -1;
+    const int Tz = std::max(T, cb.tcap);  // (targets added later within the capacity have no lists either)
+    if (Tz > 0 && hipMemsetAsync(cb.ok, 0, (size_t)Tz * sizeof(uint32_t), st) != hipSuccess) return -1;
     if (hipMemsetAsync(cb.tail, 0, 2 * sizeof(uint32_t), st) != hipSuccess) return -1;
     return 0;
   }
@@ -642,6 +643,55 @@ __global__ __launch_bounds__(256) void targets_scatter_kernel(const int* __restr
 void launch_scatter_targets(const int* idx, const float* pos, int K, float* targets, int T, int* tsel, hipStream_t st) {
   if (K <= 0) return;
   hipLaunchKernelGGL(targets_scatter_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, idx, pos, K, targets, T, tsel);
+}
+
+// A count-changing target sync (TargetResizeArgs). Workgroup 0 scatters the positions and copies
+// the build selection; workgroup 1 + m * kMoveChunks + c copies chunk c of move m's list block: a
+// target's kCellStride starts are 16-B aligned (the arrays are 256-B aligned, kCellStride * 4 is a
+// multiple of 16), so each work-item moves four uint4, loaded before the first store. The starts
+// are absolute arena offsets and the entries carry no target index: the arena is not touched.
+constexpr int kMoveVecs = kCellStride / 4;  // uint4 per block
+constexpr int kMoveChunk = 4 * 256;         // uint4 per workgroup
+constexpr int kMoveChunks = (kMoveVecs + kMoveChunk - 1) / kMoveChunk;
+static_assert(kCellStride % 4 == 0, "a target's starts are whole uint4");
+__global__ __launch_bounds__(256) void targets_resize_kernel(TargetResizeArgs a) {
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0) {
+    for (int j = tid; j < a.K; j += 256) {
+      const int t = a.idx[j];
+      if (t < 0 || t >= a.tcap) continue;
+      a.targets[3 * t] = a.pos[3 * j];
+      a.targets[3 * t + 1] = a.pos[3 * j + 1];
+      a.targets[3 * t + 2] = a.pos[3 * j + 2];
+    }
+    for (int r = tid; r < a.R; r += 256) a.tsel[r] = a.sel[r];
+    return;
+  }
+  const int m = ((int)blockIdx.x - 1) / kMoveChunks, ch = ((int)blockIdx.x - 1) - m * kMoveChunks;
+  if (m >= a.M) return;  // (workgroup-uniform)
+  const int2 mv = a.moves[m];
+  if (mv.x < 0 || mv.x >= a.tcap || mv.y < 0 || mv.y >= a.tcap || mv.x == mv.y) return;
+  const uint4* src = reinterpret_cast<const uint4*>(a.start + (size_t)mv.x * kCellStride);
+  uint4* dst = reinterpret_cast<uint4*>(a.start + (size_t)mv.y * kCellStride);
+  uint4 v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = ch * kMoveChunk + k * 256 + tid;
+    v[k] = i < kMoveVecs ? src[i] : make_uint4(0u, 0u, 0u, 0u);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = ch * kMoveChunk + k * 256 + tid;
+    if (i < kMoveVecs) dst[i] = v[k];
+  }
+  if (ch == 0 && tid == 0) {
+    a.far[mv.y] = a.far[mv.x];
+    a.ok[mv.y] = a.ok[mv.x];
+  }
+}
+void launch_resize_targets(const TargetResizeArgs& a, hipStream_t st) {
+  if (a.K <= 0 && a.R <= 0 && a.M <= 0) return;
+  hipLaunchKernelGGL(targets_resize_kernel, dim3((unsigned)(1 + std::max(a.M, 0) * kMoveChunks)), dim3(256), 0, st, a);
 }
 
 size_t cells_geo_bytes(int T, int C) {  // the CellGeo records, then the packed face rectangles (cell_rects)

@@ -68,6 +68,11 @@ struct Carver {
 // Scalars of one frame that the kernels need, plus the derived batch tables.
 struct Frame {
   int R = 0, H = 0, T = 0, TC = 0, bs = 0, nb = 0;
+  // Target capacity of a resident-target scene bound after art_targets_reserve (>= T): every
+  // T-sized device section is sized by it, and a target sync whose count stays in [1, Tc] keeps the
+  // scene bound. 0: nothing reserved (sections sized by T, a count change unbinds).
+  int Tc = 0;
+  int tcap() const { return Tc > 0 ? Tc : T; }
   int ns = 0, na = 0, no = 0;
   uint32_t stages = 0;
   bool resident = false;               // colliders come from the resident store (art_colliders.h)
@@ -218,6 +223,12 @@ struct TargetStore {
   bool store_synced = false;
   std::vector<float> snap;        // synced * 3: the positions at the last sync
   art_target_sync_stats last_sync{};
+  // identity of the mirror's targets since the last sync: src[i] is the synced index target i held
+  // then, -1 for a target added since (add appends -1, a swap-back carries the last one's along)
+  std::vector<int> src;           // count
+  std::vector<int> last_map;      // synced: src at the last sync (art_debug_target_sync_map)
+  int reserved = 0;               // art_targets_reserve
+  art_target_resize_stats last_resize{};
 };
 
 }  // namespace art
@@ -246,6 +257,10 @@ struct art_ctx {
   art_test_counts last_counts{};
   bool has_counts = false;
   std::vector<uint64_t> nonowned;  // per type (s, a, o): sum over targets of non-owned colliders
+  // audio_target_id histogram (index = id + 32768) per kind of the colliders a scene bound from desc
+  // arrays holds (the resident store keeps its own, ColliderStore::tid_hist): which target indices
+  // own colliders, for a count-changing target sync
+  std::vector<int> bind_tid_hist[3];
   art::ColliderStore store;
   art::TargetStore targets;
   // Host phases of the Unity-facing frame (ART_HOST_TIMES=1 in the environment at art_create:
@@ -283,7 +298,9 @@ int fail(art_ctx* c, int code, const char* fmt, ...) __attribute__((format(print
 int validate_desc(art_ctx* c, const art_frame_desc* d);
 FanLayout make_layout(const art_frame_desc* d, uint32_t out_flags);
 void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts = nullptr,
-                bool resident_targets = false);
+                bool resident_targets = false, int target_capacity = 0);
+// True when the permeation slot table of f (Frame::slot_batch) is the same for T targets.
+bool slot_tables_hold(const Frame& f, int T);
 void pack_inputs(const art_frame_desc* d, const Frame& f, uint8_t* h);
 struct ConeTable {
   CellCone cone[kCells];

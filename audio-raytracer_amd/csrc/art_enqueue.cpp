@@ -87,7 +87,9 @@ int enqueue_kernels(art_ctx* c, Device& dv, const Frame& f, const float* d_origi
   // nearest_first_kernel of each fast-path chunk, by one memset before the reference-order kernel
   const size_t acc_words = ((size_t)fan_count * acc_per_fan + 3) & ~(size_t)3;
   const size_t acc_bytes = acc_words * sizeof(uint32_t) + 16 + 8 * kEchoCountSlots;  // + 4 pair counters + the echo replay's counts
-  if (!dv.acc.reserve(acc_bytes)) return fail(c, ART_E_NOMEM, "device allocation failed");
+  // (room for the scene's target capacity, so that a count change within it allocates nothing)
+  const size_t acc_room = ((((size_t)fan_count * f.TC * f.tcap() + 3) & ~(size_t)3)) * sizeof(uint32_t) + 16 + 8 * kEchoCountSlots;
+  if (!dv.acc.reserve(std::max(acc_bytes, acc_room))) return fail(c, ART_E_NOMEM, "device allocation failed");
   uint32_t* acc = static_cast<uint32_t*>(dv.acc.p);
   uint32_t* pair_count = acc + acc_words;
   DevCounts* counts = nullptr;
@@ -112,6 +114,8 @@ int enqueue_kernels(art_ctx* c, Device& dv, const Frame& f, const float* d_origi
     if (int rc = ensure_side(c, dv.echo)) return rc;
     FrameParams fps = fp;
     fps.S = std::min(fan_count, chunk);
+    // (the pair buffer depends on T only through the fan chunk, which is largest at T = 1)
+    if (f.Tc > 0) fps.S = std::min(fan_count, fast_fans_per_launch(f.R, f.H, 1, f.TC, f.L.stride));
     if (!dv.pairs.reserve(fast_pair_bytes(fps))) return fail(c, ART_E_NOMEM, "device allocation failed");
   }
   // The permeation job (read-only scene and origins, writes only the fans' permeation sections)

@@ -139,7 +139,20 @@ const ConeTable& cone_table() {
 }
 
 // Frame scalars + batch tables (Audio/AudioRayTracer.cs:161, Jobs/*:63-64, :36-37).
-void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts, bool resident_targets) {
+// The permeation batch count (TC * T) / cnt / T equals floor(TC / cnt) for every T >= 1 (nested
+// floor division: floor(floor(a T / c) / T) = floor(a / c)), so the slot table does not depend on
+// the target count; checked, not assumed, by a count-changing target sync.
+bool slot_tables_hold(const Frame& f, int T) {
+  if (T < 1) return false;
+  for (int start = 0; start < f.R; start += f.bs) {
+    const int cnt = std::min(f.bs, f.R - start);
+    if ((long long)f.TC * T / cnt / T != (long long)f.TC * f.T / cnt / f.T) return false;
+  }
+  return true;
+}
+
+void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts, bool resident_targets,
+                int target_capacity) {
   // the direction-coherent order of the last frame is kept while its directions stay the same
   // (they are set once at init, AudioRayTracer.cs:72-86): a 3-KB compare instead of the sort
   std::vector<int> last_order;
@@ -151,6 +164,7 @@ void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int
   f.TC = d->batch_slots; f.bs = d->batch_size; f.nb = (f.R + f.bs - 1) / f.bs;
   f.ns = d->sphere_count; f.na = d->aabb_count; f.no = d->obb_count;
   f.res_targets = resident_targets;
+  if (resident_targets && target_capacity > 0) f.Tc = std::max(target_capacity, f.T);
   if (resident_counts) {
     f.resident = true;
     f.ns = resident_counts[0]; f.na = resident_counts[1]; f.no = resident_counts[2];
@@ -205,7 +219,7 @@ void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int
   f.off_sph = o; o = align_up(o + sn * sizeof(art_sphere), 16);
   f.off_aabb = o; o = align_up(o + an * sizeof(art_aabb), 16);
   f.off_obb = o; o = align_up(o + on * sizeof(art_obb), 16);
-  f.off_tgt = o; o = align_up(o + (size_t)f.T * 12, 16);
+  f.off_tgt = o; o = align_up(o + (size_t)f.tcap() * 12, 16);
   f.off_dirs = o; o = align_up(o + (size_t)f.R * sizeof(art_half3), 16);
   f.off_vol = o; o = align_up(o + (size_t)p.vol_n * 4, 16);
   f.off_muf = o; o = align_up(o + (size_t)p.muf_n * 4, 16);
@@ -213,7 +227,8 @@ void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int
   f.off_reset = o; o = align_up(o + (size_t)f.TC, 16);
   f.off_order = o; o = align_up(o + (size_t)f.R * 4, 16);
   f.raw_bytes = o;
-  f.cells_cap = (uint32_t)cells_entry_cap(f.T, f.ns + f.na + f.no, f.res_targets);
+  // (by the target capacity: whether the scene has lists, and their room, hold for every count it takes)
+  f.cells_cap = (uint32_t)cells_entry_cap(f.tcap(), f.ns + f.na + f.no, f.res_targets);
   Carver sizes{0};
   carve_decoded(sizes, f);
   carve_sort(sizes, f);
@@ -256,21 +271,23 @@ SortBufs carve_sort(Carver& c, const Frame& f) {
 }
 
 CellBufs carve_cells(Carver& c, const Frame& f) {
-  const size_t cells = (size_t)f.T * kCellStride;  // counters per (target, cell, collider type), with the pads
+  const size_t T = (size_t)f.tcap();
+  const size_t cells = T * kCellStride;  // counters per (target, cell, collider type), with the pads
   CellBufs cb{};
   cb.cap = f.cells_cap;
+  cb.tcap = (int)T;
   cb.count = c.take<uint32_t>((cells + 1) * 4);
   cb.start = c.take<uint32_t>((cells + 1) * 4);
   cb.cursor = c.take<uint32_t>((cells + 1) * 4);
   cb.keys = c.take<uint32_t>((size_t)cb.cap * 8);
   cb.ent_s = c.take<uint2>((size_t)cb.cap * 8);
-  cb.far = c.take<float>((size_t)f.T * 4);
-  cb.ok = c.take<uint32_t>((size_t)f.T * 4);
-  cb.tcount = c.take<unsigned long long>((size_t)f.T * 8);
+  cb.far = c.take<float>(T * 4);
+  cb.ok = c.take<uint32_t>(T * 4);
+  cb.tcount = c.take<unsigned long long>(T * 8);
   cb.box = c.take<CullRec>(sizeof(CullRec));
   cb.tail = c.take<uint32_t>(2 * sizeof(uint32_t));
   cb.ent = c.take<uint2>((size_t)cb.cap * 8);
-  cb.geo = c.take<void>(cells_geo_bytes(f.T, f.ns + f.na + f.no));
+  cb.geo = c.take<void>(cells_geo_bytes((int)T, f.ns + f.na + f.no));
   return cb;
 }
 

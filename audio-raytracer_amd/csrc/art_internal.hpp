@@ -234,6 +234,7 @@ struct CellBufs {
   uint32_t* tail;                 // [2] device: entries in use, targets dropped for capacity
   uint32_t* status;               // [2] the same pair in pinned host memory as the device sees it (or
                                   //     nullptr), written by the scan kernel and read by the host without waiting
+  int tcap;                       // the targets the per-target arrays above have room for (>= the scene's T)
 };
 size_t cells_geo_bytes(int T, int C);
 bool cells_enabled(int T, int C);
@@ -246,6 +247,20 @@ int launch_build_cells_targets(DevScene& sc, const CellBufs& cb, const int* d_ts
 // positions[idx[j]] = pos[j] and tsel[j] = idx[j] for j < K (float3 each; idx and pos may be
 // pinned host memory, tsel is device memory of at least K ints).
 void launch_scatter_targets(const int* idx, const float* pos, int K, float* targets, int T, int* tsel, hipStream_t st);
+// A target sync that changes the count, one launch from the update image (idx, pos, sel, moves may
+// be pinned host memory): positions[idx[j]] = pos[j] for j < K; tsel[r] = sel[r] for r < R (the
+// targets whose lists are built after it); and for m < M the self-contained list block of target
+// moves[m].x (its kCellStride list starts, cell_far, cell_ok) copied to target moves[m].y. The
+// sources are distinct and no source is another move's destination (the swap-back invariant,
+// DESIGN.md §3b-targets), so the copies run in parallel in place. Indices outside [0, tcap) are skipped.
+struct TargetResizeArgs {
+  const int* idx; const float* pos; int K;
+  const int* sel; int R;
+  const int2* moves; int M;
+  float* targets; int tcap; int* tsel;
+  uint32_t* start; float* far; uint32_t* ok;  // the bound scene's CellBufs arrays (unused when M == 0)
+};
+void launch_resize_targets(const TargetResizeArgs& a, hipStream_t st);
 
 // Per-fan output block (byte offsets inside one fan's record; fan f starts at f * stride).
 struct FanLayout {

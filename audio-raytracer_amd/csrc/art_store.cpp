@@ -313,7 +313,33 @@ struct TargetSyncPlan {
   bool image;
   size_t off_idx, off_pos, bytes;
   RingSlot ring;
+  // the list's edits since the last sync: every final index's synced index then (-1: new)
+  std::vector<int> map;
+  int added, removed;
+  // A count change that every bound device follows in place (the scene was bound with a target
+  // capacity and the count stays within it): the positions that travel, the targets whose lists are
+  // built at their final index, and the survivors whose lists move from their old index.
+  bool resize;
+  std::vector<int> up;       // new, re-indexed or moved in space, ascending
+  std::vector<int> sel;      // new, moved in space, or re-indexed onto / from an index that colliders name
+  std::vector<int2> moves;   // (old index, new index)
+  size_t off_sel, off_mov;   // further sections of the update image: [sel][moves]
 };
+
+// Colliders of the bound scene whose audio_target_id is `index` (the store's histogram of the synced
+// records, or the one art_scene_bind made of the desc's arrays; without one: as if owned).
+bool index_owns_colliders(const art_ctx& c, int index) {
+  long long owned = 0;
+  for (int k = 0; k < 3; ++k) {
+    const std::vector<int>& h = c.fr.resident ? c.store.tid_hist[k] : c.bind_tid_hist[k];
+    if (h.empty()) {
+      if (!c.fr.resident) return true;
+      continue;
+    }
+    owned += h[(size_t)(index + 32768)];
+  }
+  return owned > 0;
+}
 
 TargetSyncPlan plan_target_sync(art_ctx& c) {
   TargetStore& t = c.targets;
@@ -324,12 +350,36 @@ TargetSyncPlan plan_target_sync(art_ctx& c) {
     if (i < p.n && t.dirty[(size_t)i]) p.moved.push_back(i);
   std::sort(p.moved.begin(), p.moved.end());
   p.moved.erase(std::unique(p.moved.begin(), p.moved.end()), p.moved.end());
-  bool bound = false;
-  for (const Device& dv : c.devs) bound |= dv.bound;
-  p.image = !c.cpu && bound && c.fr.res_targets && !p.count_changed && !p.moved.empty();
+  p.map.assign(t.src.begin(), t.src.begin() + p.n);
+  p.added = (int)std::count(p.map.begin(), p.map.end(), -1);
+  p.removed = (t.store_synced ? t.synced : 0) - (p.n - p.added);
+  bool bound = false, follow = true;
+  for (const Device& dv : c.devs) {
+    bound |= dv.bound;
+    follow &= !dv.bound || (dv.sc.T == t.synced && p.n <= dv.cb.tcap);
+  }
+  const Frame& f = c.fr;
+  p.resize = !c.cpu && bound && follow && f.res_targets && p.count_changed && t.store_synced && f.Tc > 0 && p.n >= 1 &&
+             p.n <= f.Tc && slot_tables_hold(f, p.n);
+  if (p.resize)
+    for (int i = 0; i < p.n; ++i) {
+      const int s = p.map[(size_t)i];
+      const bool fresh = s < 0 || memcmp(t.pos.data() + (size_t)i * 3, t.snap.data() + (size_t)s * 3, 12) != 0;
+      if (!fresh && s == i) continue;  // unchanged
+      p.up.push_back(i);
+      // a block built at index s holds the colliders not owned by s: it is index i's only if no
+      // collider names either (cells_geo_kernel drops those of the target's own index)
+      if (fresh || index_owns_colliders(c, s) || index_owns_colliders(c, i)) p.sel.push_back(i);
+      else p.moves.push_back(make_int2(s, i));
+    }
+  p.image = !c.cpu && bound && f.res_targets && ((!p.count_changed && !p.moved.empty()) || p.resize);
+  const size_t K = p.resize ? p.up.size() : p.moved.size();
   p.off_idx = 0;
-  p.off_pos = align_up(p.moved.size() * 4, 16);
-  p.bytes = p.image ? align_up(p.off_pos + p.moved.size() * 12, 16) : 0;
+  p.off_pos = align_up(K * 4, 16);
+  p.off_sel = align_up(p.off_pos + K * 12, 16);
+  p.off_mov = align_up(p.off_sel + p.sel.size() * 4, 16);
+  // (at least one section's worth: removing the last target changes the count and uploads nothing)
+  p.bytes = p.image ? std::max<size_t>(16, align_up(p.off_mov + p.moves.size() * sizeof(int2), 16)) : 0;
   p.ring = p.image ? take_ring_slot(c.store) : RingSlot{-1, 0};
   return p;
 }
@@ -339,18 +389,22 @@ int stage_target_image(art_ctx* c, const TargetSyncPlan& p) {
   HostBuf& hb = c->store.h_upd[p.ring.slot];
   if (!hb.reserve(p.bytes)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
   uint8_t* h = static_cast<uint8_t*>(hb.p);
-  for (size_t j = 0; j < p.moved.size(); ++j) {
-    const int i = p.moved[j];
+  const std::vector<int>& ids = p.resize ? p.up : p.moved;
+  for (size_t j = 0; j < ids.size(); ++j) {
+    const int i = ids[j];
     memcpy(h + p.off_idx + j * 4, &i, 4);
     memcpy(h + p.off_pos + j * 12, c->targets.pos.data() + (size_t)i * 3, 12);
   }
+  if (!p.sel.empty()) memcpy(h + p.off_sel, p.sel.data(), p.sel.size() * 4);
+  if (!p.moves.empty()) memcpy(h + p.off_mov, p.moves.data(), p.moves.size() * sizeof(int2));
   return ART_OK;
 }
 
 // One device's share of a moved-targets sync, async on the stream it picks (as sync_device): one
 // launch scatters the positions from the pinned image into the bound scene's target array, then
-// the moved targets' cell lists are rebuilt on their own (or every target's: full).
-int sync_device_targets(art_ctx* c, Device& dv, const TargetSyncPlan& p, int& rebuilt, bool& full_rebuild) {
+// the moved targets' cell lists are rebuilt on their own (or every target's: full). A count change
+// that the scene follows (p.resize) takes the first branch.
+int sync_device_targets(art_ctx* c, Device& dv, const TargetSyncPlan& p, int& rebuilt, bool& full_rebuild, int& lists_moved) {
   StoreDev& s = dv.store;
   HIP_TRY(c, hipSetDevice(dv.id));
   const hipStream_t ss = (dv.fence.pending && !dv.fence.recorded) ? dv.fence.stream : dv.stream;
@@ -359,6 +413,47 @@ int sync_device_targets(art_ctx* c, Device& dv, const TargetSyncPlan& p, int& re
   s.stream = ss;
   EpochMark epoch{s, p.ring, ss};
   if (!dv.bound) return epoch.record(c);
+  if (p.resize) {
+    // A count change within the scene's capacity: one launch scatters the positions and moves the
+    // list blocks of the survivors that may keep theirs (before the builds below, which may write a
+    // move's source), then the selected targets' lists are built at their final index, or every
+    // target's (the existing rule, with the new count). Nothing is allocated.
+    const int K = (int)p.sel.size();
+    if (!dv.tsel.reserve((size_t)kMaxTargets * sizeof(int))) return fail(c, ART_E_NOMEM, "device allocation failed");
+    const bool lists = dv.cb.cap > 0;
+    bool full = false;
+    if (lists) {
+      if (p.removed > 0) dv.cells_partial = true;  // a removed target's entries are garbage in the arena
+      const volatile uint32_t* status = static_cast<const volatile uint32_t*>(dv.cell_status.p);
+      const uint32_t tail = status ? status[0] : 0u, dropped = status ? status[1] : 0u;
+      full = dropped > 0u || (dv.cells_partial && tail > dv.cb.cap / kArenaCompactDen * kArenaCompactNum) ||
+             4 * K >= kFullBuildNum * p.n;
+    }
+    void* hd = nullptr;  // the pinned image as the device sees it
+    HIP_TRY(c, hipHostGetDevicePointer(&hd, c->store.h_upd[p.ring.slot].p, 0));
+    const uint8_t* u = static_cast<const uint8_t*>(hd);
+    TargetResizeArgs a{};
+    a.idx = reinterpret_cast<const int*>(u + p.off_idx); a.pos = reinterpret_cast<const float*>(u + p.off_pos); a.K = (int)p.up.size();
+    a.sel = reinterpret_cast<const int*>(u + p.off_sel); a.R = lists && !full ? K : 0;
+    a.moves = reinterpret_cast<const int2*>(u + p.off_mov); a.M = lists && !full ? (int)p.moves.size() : 0;
+    a.targets = const_cast<float*>(dv.sc.targets); a.tcap = dv.cb.tcap; a.tsel = static_cast<int*>(dv.tsel.p);
+    a.start = dv.cb.start; a.far = dv.cb.far; a.ok = dv.cb.ok;
+    launch_resize_targets(a, ss);
+    HIP_TRY(c, hipGetLastError());
+    dv.sc.T = dv.sorted.sc.T = p.n;
+    dv.last.valid = false;
+    if (lists) {
+      const int rc = full ? launch_build_cells(dv.sc, dv.cb, ss)
+                          : launch_build_cells_targets(dv.sc, dv.cb, static_cast<const int*>(dv.tsel.p), K, ss);
+      if (rc != 0) return fail(c, ART_E_DEVICE, "muffle cell lists failed");
+      dv.cells_partial = !full;
+      if (full) full_rebuild = true;
+      else { rebuilt = K; lists_moved = a.M; }
+    }
+    if (!s.done) HIP_TRY(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    if (ss == dv.stream) HIP_TRY(c, hipEventRecord(s.done, ss));
+    return epoch.record(c);
+  }
   const int K = (int)p.moved.size();
   if (dv.sc.T != p.n || K > kMaxTargets) return fail(c, ART_E_STATE, "art_targets_sync: the bound scene's targets are not the store's");
   if (!dv.tsel.reserve((size_t)kMaxTargets * sizeof(int))) return fail(c, ART_E_NOMEM, "device allocation failed");
@@ -387,23 +482,55 @@ int sync_device_targets(art_ctx* c, Device& dv, const TargetSyncPlan& p, int& re
   return epoch.record(c);
 }
 
-void commit_target_sync(art_ctx* c, const TargetSyncPlan& p, int rebuilt, bool full_rebuild) {
+void commit_target_sync(art_ctx* c, const TargetSyncPlan& p, int rebuilt, bool full_rebuild, int lists_moved) {
   TargetStore& t = c->targets;
+  bool was_bound = false;
+  for (const Device& dv : c->devs) was_bound |= dv.bound;
   for (int i : t.dirty_list)
     if ((size_t)i < t.dirty.size()) t.dirty[(size_t)i] = 0;
   t.dirty_list.clear();
   t.synced = p.n;
   t.snap.assign(t.pos.begin(), t.pos.begin() + (size_t)p.n * 3);  // the JobBatch snapshot frames read
   t.store_synced = true;
-  if (p.count_changed && c->fr.res_targets)
+  if (p.resize) {
+    // The host frame follows: only T and the fan layout depend on the count (the batch slot tables do
+    // not, slot_tables_hold). make_frame is not called: it reads the caller's direction array.
+    Frame& f = c->fr;
+    f.T = f.fp.T = p.n;
+    art_frame_desc tmp{};
+    tmp.ray_count = f.R; tmp.max_hits_per_ray = f.H; tmp.audio_target_count = f.T; tmp.batch_slots = f.TC;
+    tmp.stages = f.stages;
+    f.L = make_layout(&tmp, f.L.has_hits ? ART_OUT_HIT_RESULTS : 0u);
+    c->nonowned.assign(3, 0);  // (counting frames: colliders not owned, summed over the new targets)
+    const int n[3] = {f.ns, f.na, f.no};
+    for (int k = 0; k < 3; ++k) {
+      const std::vector<int>& h = f.resident ? c->store.tid_hist[k] : c->bind_tid_hist[k];
+      uint64_t owned = 0;
+      for (int i = 0; i < p.n && !h.empty(); ++i) owned += (uint64_t)h[(size_t)i + 32768];
+      c->nonowned[(size_t)k] = (uint64_t)p.n * (uint64_t)n[k] - owned;
+    }
+  } else if (p.count_changed && c->fr.res_targets) {
     for (Device& dv : c->devs) dv.bound = false;  // T is in the frame layout: bind again
+  }
+  t.last_map = p.map;
+  for (int i = 0; i < p.n; ++i) t.src[(size_t)i] = i;
   // a full rebuild used the colliders' synced records: they are the lists' base now
   if (full_rebuild && c->fr.resident) snapshot_cell_base(c);
   t.last_sync.dirty_targets = (int32_t)p.moved.size();
   t.last_sync.count_changed = p.count_changed ? 1 : 0;
   t.last_sync.lists_rebuilt = rebuilt;
   t.last_sync.lists_full_rebuild = full_rebuild ? 1 : 0;
-  t.last_sync.bytes_uploaded = p.image ? p.moved.size() * 16 : 0;
+  const bool resize_image = p.resize && (!p.up.empty() || !p.sel.empty() || !p.moves.empty());
+  t.last_sync.bytes_uploaded = p.resize ? (resize_image ? p.bytes : 0) : p.image ? p.moved.size() * 16 : 0;
+  bool is_bound = false;
+  for (const Device& dv : c->devs) is_bound |= dv.bound;
+  t.last_resize.kept_bound = (was_bound && is_bound && c->fr.res_targets) ? 1 : 0;
+  t.last_resize.added = p.added;
+  t.last_resize.removed = p.removed;
+  t.last_resize.lists_moved = lists_moved;
+  t.last_resize.lists_rebuilt = rebuilt;
+  t.last_resize.lists_full_rebuild = full_rebuild ? 1 : 0;
+  t.last_resize.bytes_uploaded = t.last_sync.bytes_uploaded;
 }
 
 }  // namespace
@@ -418,6 +545,7 @@ ART_API int art_target_add(art_ctx* c, const float pos[3], int32_t* out_id) {
   t.pos.insert(t.pos.end(), pos, pos + 3);
   t.dirty.push_back(1);
   t.dirty_list.push_back(t.count);
+  t.src.push_back(-1);
   if (out_id) *out_id = t.count;  // the index in the list (AudioTargetRT.cs:40-44)
   t.count++;
   return ART_OK;
@@ -450,10 +578,12 @@ ART_API int art_target_remove_swapback(art_ctx* c, int32_t id) {
   if (id != last) {  // AudioTargetManager.cs:67-73
     memcpy(t.pos.data() + (size_t)id * 3, t.pos.data() + (size_t)last * 3, 12);
     if (!t.dirty[(size_t)id]) { t.dirty[(size_t)id] = 1; t.dirty_list.push_back(id); }
+    t.src[(size_t)id] = t.src[(size_t)last];  // the same target, at a new index
   }
   t.count = last;
   t.pos.resize((size_t)last * 3);
   t.dirty.resize((size_t)last);
+  t.src.resize((size_t)last);
   return ART_OK;
 }
 
@@ -473,7 +603,7 @@ ART_API int art_target_synced_count(art_ctx* c) { return c ? c->targets.synced :
 ART_API int art_targets_clear(art_ctx* c) {
   if (!c) return ART_E_INVALID;
   TargetStore& t = c->targets;
-  t.pos.clear(); t.dirty.clear(); t.dirty_list.clear(); t.count = 0;
+  t.pos.clear(); t.dirty.clear(); t.dirty_list.clear(); t.src.clear(); t.count = 0;
   return ART_OK;
 }
 
@@ -487,15 +617,39 @@ ART_API int art_targets_sync(art_ctx* c) {
   if (!c) return ART_E_INVALID;
   if (c->inflight) return fail(c, ART_E_STATE, "art_targets_sync: a frame is in flight (sync after art_complete)");
   const TargetSyncPlan p = plan_target_sync(*c);
-  int rebuilt = 0;
+  int rebuilt = 0, lists_moved = 0;
   bool full_rebuild = false;
   if (p.image) {
     if (int rc = stage_target_image(c, p)) return rc;
     for (Device& dv : c->devs)
-      if (int rc = sync_device_targets(c, dv, p, rebuilt, full_rebuild)) return rc;
+      if (int rc = sync_device_targets(c, dv, p, rebuilt, full_rebuild, lists_moved)) return rc;
   }
-  commit_target_sync(c, p, rebuilt, full_rebuild);
+  commit_target_sync(c, p, rebuilt, full_rebuild, lists_moved);
   return ART_OK;
+}
+
+ART_API int art_targets_reserve(art_ctx* c, int32_t capacity) {
+  if (!c) return ART_E_INVALID;
+  if (capacity < 0) return fail(c, ART_E_INVALID, "art_targets_reserve: negative capacity");
+  if (capacity > kMaxTargets) return fail(c, ART_E_UNSUPPORTED, "art_targets_reserve: capacity > %d", kMaxTargets);
+  if (c->inflight) return fail(c, ART_E_STATE, "art_targets_reserve: a frame is in flight (reserve after art_complete)");
+  c->targets.reserved = capacity;
+  return ART_OK;
+}
+
+ART_API int art_target_capacity(art_ctx* c) { return c ? c->targets.reserved : ART_E_INVALID; }
+
+ART_API int art_targets_last_resize(art_ctx* c, art_target_resize_stats* out) {
+  if (!c || !out) return ART_E_INVALID;
+  *out = c->targets.last_resize;
+  return ART_OK;
+}
+
+ART_API int art_debug_target_sync_map(art_ctx* c, int32_t* src, int32_t cap) {
+  if (!c || cap < 0 || (cap > 0 && !src)) return ART_E_INVALID;
+  const std::vector<int>& m = c->targets.last_map;
+  for (int32_t i = 0; i < cap && (size_t)i < m.size(); ++i) src[i] = m[(size_t)i];
+  return c->targets.synced;
 }
 
 ART_API int art_collider_add(art_ctx* c, int32_t kind, const void* rec, int32_t* out_id) {

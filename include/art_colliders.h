@@ -142,7 +142,9 @@ ART_API int art_targets_clear(art_ctx* ctx);
 /* UpdateJobBatch (:105-110): publish the mirror to every device of the context. Stream-ordered
  * exactly like art_colliders_sync (the same stream choice and fences). ART_E_STATE while a frame is
  * in flight. A count change (add, remove, clear) unbinds a bound resident-target scene: T is part
- * of the frame layout, so the next art_scene_bind / art_schedule builds everything again. */
+ * of the frame layout, so the next art_scene_bind / art_schedule builds everything again — unless
+ * the scene was bound with a reserved capacity (art_targets_reserve, below) and the count stays
+ * within it. */
 ART_API int art_targets_sync(art_ctx* ctx);
 
 /* What the last art_targets_sync moved. */
@@ -159,6 +161,44 @@ ART_API int art_targets_last_sync(art_ctx* ctx, art_target_sync_stats* out);
 /* Diagnostics (synchronizes device 0): entries in use and capacity of the bound scene's muffle
  * cell-list arena, and the targets currently without lists because theirs did not fit. */
 ART_API int art_debug_cells_arena(art_ctx* ctx, uint64_t* used, uint64_t* cap, uint32_t* dropped_targets);
+
+/* ------------------------------------------- targets that appear and disappear (ABI 3.7) */
+
+/* Room for up to `capacity` targets in scenes bound from now on with ART_CTX_RESIDENT_TARGETS:
+ * a later art_targets_sync whose count stays in [1, capacity] keeps such a scene bound (it adds,
+ * removes and re-indexes the targets on the device, stream-ordered like a move, and allocates
+ * nothing). A scene bound with more targets than `capacity` is sized by its own count, and that
+ * count is its capacity. 0 (the default) = a count change unbinds, as above. Does not touch a
+ * scene that is already bound.
+ * ART_E_INVALID for capacity < 0, ART_E_UNSUPPORTED above the target limit (256),
+ * ART_E_STATE while a frame is in flight.
+ *
+ * What stays with the caller after a count change that kept the scene bound:
+ *  - the fan-block stride follows the synced count: re-query art_fan_layout_get with
+ *    art_target_synced_count (as after a rebind) and size d_block for it;
+ *  - the tick's and the mix's source numbering s = f * T + t changes with T: re-packing d_state
+ *    and d_volume for the new numbering;
+ *  - re-numbering the audio_target_id of the colliders a swapped target owns (art_collider_set),
+ *    as art_target_remove_swapback says. */
+ART_API int art_targets_reserve(art_ctx* ctx, int32_t capacity);
+ART_API int art_target_capacity(art_ctx* ctx);          /* the reserved capacity, or < 0 */
+
+/* What the last art_targets_sync did to the list and to a bound scene's lists. */
+typedef struct {
+    int32_t kept_bound;     /* 1: the bound scene followed the count change; 0: it was unbound (or none was bound) */
+    int32_t added;          /* synced targets that did not exist at the previous sync */
+    int32_t removed;        /* previously synced targets that no longer exist */
+    int32_t lists_moved;    /* surviving targets whose index changed and whose lists were moved, not rebuilt */
+    int32_t lists_rebuilt;  /* targets whose lists were built on their own (new, re-indexed-but-owned, or moved in space) */
+    int32_t lists_full_rebuild;
+    uint64_t bytes_uploaded;
+} art_target_resize_stats;
+ART_API int art_targets_last_resize(art_ctx* ctx, art_target_resize_stats* out);
+
+/* Diagnostics (tests; host only, works on the CPU backend): for each synced index i < cap, the synced
+ * index the same target held before the last art_targets_sync, or -1 if it is new.
+ * Returns the synced count. */
+ART_API int art_debug_target_sync_map(art_ctx* ctx, int32_t* src, int32_t cap);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,13 @@ The moving-target step, timed the same way:
     python3 tools/dynamic_run.py [config] [steps] --targets K            K of the T targets moved per step:
                                  art_target_set_many + art_targets_sync + art_launch_device
     python3 tools/dynamic_run.py [config] [steps] --targets K --rebind   the same step without the target
-                                 store: art_scene_bind with the new positions + art_launch_device"""
+                                 store: art_scene_bind with the new positions + art_launch_device
+Targets that spawn and despawn (a scene bound with a reserved capacity follows the count):
+    python3 tools/dynamic_run.py [config] [steps] --spawn [--extra E] [--remove I] [--rebind]
+                                 steps alternately add one target and remove-swapback target I (default 0: the
+                                 spawned one lands on an index that colliders name, its lists are rebuilt); with
+                                 --extra 1 --remove T the config's T + 1 targets and target T owns nothing: its
+                                 successor's lists move. --rebind: art_scene_bind with each step's list instead."""
 import os
 import sys
 import time
@@ -85,8 +91,79 @@ def target_steps(cfg, steps, K, rebind):
     ctx.close()
 
 
+def spawn_steps(cfg, steps, rebind, extra, remove):
+    """Steps alternately add one target and remove-swapback target `remove` (the config's T + extra
+    targets and one more); `extra` targets that own no colliders are added first and stay. With the
+    store the scene is bound once with a reserved capacity; --rebind binds each step's list."""
+    scene, org, params = art.synth(cfg)
+    S = org.shape[0]
+    rng = np.random.default_rng(7)
+    lo, hi = scene.targets.min(axis=0) - 2, scene.targets.max(axis=0) + 2
+    pos = [p for p in scene.targets] + [rng.uniform(lo, hi).astype(np.float32) for _ in range(extra)]
+    T0 = len(pos)
+    spawn = [rng.uniform(lo, hi).astype(np.float32) for _ in range(8)]
+    ctx = art.Context(1)
+    outs = {T: art.FanOutputs(S, cfg.R, cfg.H, T, 1, dsp=params.dsp is not None) for T in (T0, T0 + 1)}
+
+    def frame_of(p):
+        sc = art.Scene(dirs=scene.dirs, targets=np.array(p, np.float32), spheres=scene.spheres, aabbs=scene.aabbs, obbs=scene.obbs)
+        return art.Frame(sc, params, org, outs[len(p)])
+    stride = max(art.fan_layout(frame_of(pos + [spawn[0]][:k]))["stride"] for k in (0, 1))
+    d_org = torch.from_numpy(np.ascontiguousarray(org)).cuda()
+    d_blk = torch.zeros(S * stride, dtype=torch.uint8, device="cuda")
+    sp = torch.cuda.current_stream().cuda_stream
+    what = f"T {T0} <-> {T0 + 1}, add / remove-swapback {remove}"
+    if rebind:
+        frames = {}
+
+        def one(i):
+            if i % 2 == 0:
+                pos.append(spawn[(i // 2) % len(spawn)])
+            else:
+                pos[remove] = pos[-1]
+                pos.pop()
+            key = b"".join(p.tobytes() for p in pos)
+            if key not in frames:  # (the lists repeat with the eight spawn positions: made once)
+                frames[key] = frame_of(pos)
+            ctx.bind(frames[key])
+            ctx.launch_device(d_org.data_ptr(), S, d_blk.data_ptr(), 0, sp)
+        for i in range(32):  # every list of the cycle, before the timed steps
+            one(i)
+        timed(one, steps, f"{what}, art_scene_bind + launch", cfg)
+    else:
+        from art.targets import TargetStore, resident_targets_frame
+        store = TargetStore(ctx)
+        store.add_many(pos)
+        store.sync()
+        store.reserve(T0 + 1)
+        ctx.set_flags(abi.ART_CTX_RESIDENT_TARGETS)
+        ctx.bind(resident_targets_frame(frame_of(pos)))
+        stats = {}
+
+        def one(i):
+            if i % 2 == 0:
+                store.add(spawn[(i // 2) % len(spawn)])
+            else:
+                store.remove_swapback(remove)
+            store.sync()
+            rs = store.last_resize()
+            key = (rs["kept_bound"], rs["lists_moved"], rs["lists_rebuilt"], rs["lists_full_rebuild"])
+            stats[key] = stats.get(key, 0) + 1
+            ctx.launch_device(d_org.data_ptr(), S, d_blk.data_ptr(), 0, sp)
+        timed(one, steps, f"{what}, art_target_add / remove + art_targets_sync + launch", cfg)
+        print(f"  syncs by (kept_bound, lists_moved, lists_rebuilt, lists_full_rebuild): {stats}; arena {store.cells_arena()}",
+              flush=True)
+    ctx.close()
+
+
 def main():
     argv = sys.argv[1:]
+    opts = {"--extra": 0, "--remove": 0}
+    for name in opts:
+        if name in argv:
+            at = argv.index(name)
+            opts[name] = int(argv[at + 1])
+            del argv[at:at + 2]
     K = None
     if "--targets" in argv:
         at = argv.index("--targets")
@@ -95,6 +172,8 @@ def main():
     args = [a for a in argv if not a.startswith("--")]
     cfg = art.CONFIGS[int(args[0]) if len(args) > 0 else 2]
     steps = int(args[1]) if len(args) > 1 else 500
+    if "--spawn" in argv:
+        return spawn_steps(cfg, steps, "--rebind" in argv, opts["--extra"], opts["--remove"])
     if K is not None:
         return target_steps(cfg, steps, K, "--rebind" in argv)
     scene, org, params = art.synth(cfg)
