@@ -292,6 +292,15 @@ class Context:
             self._raise(rc)
         return int(rep.value), int(trav.value)
 
+    def debug_scene_r_min(self) -> float:
+        """The bound scene's lower bound of the sphere radii, as the next frame's echo replay margins use
+        it (art_debug_sphere_slack; diagnostics). inf without spheres."""
+        slack, r_min = C.c_float(), C.c_float()
+        rc = self.lib.art_debug_sphere_slack(self.ptr, C.c_float(1.0), C.c_float(1.0), C.byref(slack), C.byref(r_min))
+        if rc:
+            self._raise(rc)
+        return float(r_min.value)
+
     def launch_device(self, d_origins: int, fan_count: int, d_block: int, out_flags: int = 0, stream: int | None = None):
         rc = self.lib.art_launch_device(self.ptr, d_origins, fan_count, d_block, out_flags, stream)
         if rc:

@@ -23,6 +23,7 @@
 #include <new>
 
 #include "art_ctx.hpp"
+#include "art_frame_math.hpp"
 
 using namespace art;
 
@@ -49,8 +50,8 @@ namespace {
 // art_dsp_tick_params_host, art_dsp_settings_bind, art_dsp_tick_params_device, art_dsp_tick_device);
 // 3.6: the listener mix (art_dsp_mix_device, art_dsp_tick_mix_device, art_dsp_mix_host); 3.7: targets
 // added and removed on a bound scene (art_targets_reserve, art_target_capacity, art_targets_last_resize,
-// art_debug_target_sync_map)
-constexpr uint32_t kAbiVersion = (3u << 16) | 7u;
+// art_debug_target_sync_map); 3.8: art_debug_sphere_slack
+constexpr uint32_t kAbiVersion = (3u << 16) | 8u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -683,6 +684,16 @@ ART_API int art_debug_echo_decided(art_ctx* c, uint64_t* replayed, uint64_t* tra
       *traversed += x >> 32;
     }
   }
+  return ART_OK;
+}
+
+ART_API int art_debug_sphere_slack(art_ctx* c, float r, float D, float* slack, float* scene_r_min) {
+  if (!slack || (scene_r_min && !c)) return ART_E_INVALID;
+  *slack = art::sphere_report_slack(r, D);
+  if (!scene_r_min) return ART_OK;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) keeps no device scene", __func__);
+  if (c->devs.empty() || !c->devs[0].bound) return fail(c, ART_E_STATE, "no scene bound (art_scene_bind)");
+  *scene_r_min = c->devs[0].sc.r_min;
   return ART_OK;
 }
 

@@ -11,7 +11,8 @@
 //
 // Exactness. A collider whose float test blocks the segment contains, in its
 // widened bounding sphere (margin factor * (far_t + |h| + 1), the broad-phase factors of §5 item 8
-// applied to the rounding scale |off - c| <= maxd + |h| <= far_t + |h|), the exact point at the
+// applied to the rounding scale |off - c| <= maxd + |h| <= far_t + |h|; a sphere: the smaller of that
+// and the sphere lemma at its own radius, sphere_report_slack), the exact point at the
 // reported parameter of the float ray (off, normalize(t - off)). That ray deviates from the exact
 // segment [off, target] by at most eta = 2e-6 far_t, so the
 // collider's widened bounding sphere (+ 2 eta) meets the exact ray from the target towards `off`:
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "art_device_fns.hpp"
+#include "art_frame_math.hpp"
 
 namespace art {
 
@@ -221,7 +223,10 @@ __device__ void cells_geo_one(const DevScene& sc, const CellBufs& cb, int n, int
     h1 = hh.x + hh.y + hh.z;
     widen = 1.7321f;  // a box widened by m per axis: its half-diagonal grows by sqrt(3) m
   }
-  const float m = cr.factor * (far + r + h1 + 1.0f);
+  float m = cr.factor * (far + r + h1 + 1.0f);
+  // a sphere's own radius gives the tighter bound of the sphere lemma (sphere_report_slack), at
+  // |o - c| <= 1.002 (far_t + r): the hit point lies within far_t of o and within r + m of c, m <= 9e-4 |o - c|
+  if (ty == 0) m = fminf(m, sphere_report_slack(r, 1.002f * (far + r)));
   const float rho = r + widen * m + 2.0f * (kCellEta * far + 1e-6f) + 1e-6f * (fabsf(cc0.x) + fabsf(cc0.y) + fabsf(cc0.z)) +
                     cell_slack(r);
   const vec3 w = mk3(cc0.x - tg.x, cc0.y - tg.y, cc0.z - tg.z);

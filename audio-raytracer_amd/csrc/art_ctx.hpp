@@ -198,6 +198,9 @@ struct ColliderStore {
   std::vector<uint8_t> cell_base[3];
   bool cell_base_ok = false;
   uint64_t sync_gen = 0;         // bumped by every art_colliders_sync that changed a record
+  // lower bound of |radius| over the synced spheres (DevScene::r_min): exact after a sync that walks
+  // every record (a count change, a reallocation), lowered by the dirty spheres of any other
+  float sphere_rmin = INFINITY;
   // audio_target_id of every synced record and their histogram (index = id + 32768), kept
   // incrementally from the dirty records (permeation loss test counts of counting frames)
   std::vector<int16_t> synced_tid[3];
@@ -322,6 +325,8 @@ int scene_reader_end(art_ctx* c, Device& dv, hipStream_t st);
 int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in);
 void snapshot_cell_base(art_ctx* c);
 bool cell_still_valid(int kind, const uint8_t* now, const uint8_t* base);
+// min(bound, the smallest |radius| of the n sphere records at recs) (DevScene::r_min; a non-finite radius counts as 0)
+float spheres_rmin(const void* recs, int n, float bound);
 
 // art_enqueue.cpp
 // What an event pair of Device::ev_used times: a stage of the frame, or one kernel of the raytrace

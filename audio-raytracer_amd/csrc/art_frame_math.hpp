@@ -37,6 +37,29 @@ ART_HD CullRec make_cull(float lx, float ly, float lz, float hx, float hy, float
   return c;
 }
 
+// How far outside a sphere of radius r the reference's float test can report a hit, for a segment
+// start within D of the centre (|oc| <= D): the sphere lemma of DESIGN.md §5 item 8. The reported
+// point P satisfies |P - c|^2 <= r^2 + E, E = 13 eps |oc|^2 + 4 eps r^2 (the rounding of the
+// discriminant), plus 16 eps (r + |oc|) for the rounding of oc, of the root and of the point. Two
+// bounds follow: sqrt(r^2 + E) <= r + sqrt(E), tight only as r -> 0, which the margins have always
+// used (kCullSphere's base factor times the scale), and sqrt(r^2 + E) <= r + E / (2 r), far smaller
+// once r is not tiny against sqrt(eps) |oc|. The result is the smaller of the two, the second with a
+// safety factor of kSlackSafety; r <= 0 or non-finite keeps the first.
+#ifndef ART_SPHERE_SLACK_SCALE
+#define ART_SPHERE_SLACK_SCALE 1.0f  // test hook: 0 disables the r-aware bound's slack (tests/test_sphere_slack_gpu.py must fail)
+#endif
+constexpr float kSlackEps = 5.9604645e-8f;  // 2^-24
+constexpr float kSlackDisc = 13.0f, kSlackR2 = 4.0f, kSlackLin = 16.0f;  // E's and the linear term's constants, in eps
+constexpr float kSlackRoot = 4e-3f;    // the square-root form: 4.5 x sqrt(13 eps) = 8.8e-4
+constexpr float kSlackSafety = 2.0f;
+ART_HD float sphere_report_slack(float r, float D) {
+  const float root = kSlackRoot * D;
+  if (!(r > 0.0f) || !ufinite(r)) return root;
+  const float e = kSlackEps * (kSlackDisc * D * D + kSlackR2 * r * r);
+  const float lin = (ART_SPHERE_SLACK_SCALE * kSlackSafety) * (e / (2.0f * r) + (kSlackLin * kSlackEps) * (r + D));
+  return fminf(root, lin);
+}
+
 // Per-collider decode (shared by the full prep and the resident store's scatter): the hot/cold
 // records at in-kind index i and the broad-phase bounds at global index gi.
 ART_HD void prep_sphere(const art_sphere& s, int i, int gi, SphereRec* __restrict__ osph,

@@ -98,6 +98,10 @@ struct DevScene {
   const float* cell_far;          // [T]: the segment length the lists were built for
   const uint32_t* cell_ok;        // [T]
   uint32_t cell_cap;
+  // A lower bound of |radius| over the scene's spheres (+infinity: none), kept by the host: from the
+  // inputs at a bind, lowered by the resident store's syncs (a stale-low value only widens the echo
+  // replay's margins, log_margin_om). Like the counts above it travels in the launch's arguments.
+  float r_min;
 };
 // The colliders as the caller gives them (AoS halves) and as the kernels read them (decoded hot and
 // cold records, bounds in global order: spheres, AABBs, OBBs).

@@ -94,6 +94,17 @@ bool cell_still_valid(int kind, const uint8_t* now, const uint8_t* base) {
   return std::isfinite(d2) && std::isfinite(r2) && d2 <= half * half;
 }
 
+float spheres_rmin(const void* recs, int n, float bound) {
+  const uint8_t* p = static_cast<const uint8_t*>(recs);
+  for (int i = 0; i < n; ++i) {
+    art_sphere s;
+    memcpy(&s, p + (size_t)i * sizeof(art_sphere), sizeof s);
+    const float r = std::fabs(art::f16tof32(s.radius));
+    bound = std::isfinite(r) ? std::min(bound, r) : 0.0f;
+  }
+  return bound;
+}
+
 // The BVH of dv.sc on dv.stream: the resident scene's kept orders (refit when the store changed
 // since) or a new sort and build.
 static int build_bvh(art_ctx* c, Device& dv, const Frame& f, bool reuse) {
@@ -137,7 +148,9 @@ int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in) {
   DevScene& sc = dv.sc;
   if (f.resident) {  // records and bounds of the last art_colliders_sync
     set_colliders(sc, dv.store.dec, dv.store.n);
+    sc.r_min = c->store.sphere_rmin;
   } else {
+    sc.r_min = spheres_rmin(h_in + f.off_sph, f.ns, INFINITY);
     const RawColliders in = {reinterpret_cast<const art_sphere*>(raw + f.off_sph), reinterpret_cast<const art_aabb*>(raw + f.off_aabb),
                              reinterpret_cast<const art_obb*>(raw + f.off_obb), f.ns, f.na, f.no};
     launch_prep(in, out, dv.stream);

@@ -115,6 +115,11 @@ SyncPlan plan_sync(art_ctx& c) {
         break;
       }
   }
+  // the spheres' radius bound (DevScene::r_min): a sync that walks every record recomputes it, any
+  // other only lowers it by the dirty spheres (the mirror holds the records as the devices will)
+  if (p.counts_changed || p.fresh) s.sphere_rmin = spheres_rmin(s.kinds[0].recs.data(), p.n[0], INFINITY);
+  else
+    for (int i : p.lists[0]) s.sphere_rmin = spheres_rmin(s.kinds[0].recs.data() + (size_t)i * kRecSize[0], 1, s.sphere_rmin);
   p.ring = take_ring_slot(s);
   return p;
 }
@@ -227,6 +232,7 @@ int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt) 
     return epoch.record(c);
   }
   set_colliders(dv.sc, v.dec, p.n);  // the bound device-resident scene sees the new snapshot
+  dv.sc.r_min = c->store.sphere_rmin;
   if (!p.nd) return epoch.record(c);
   // moved colliders: refit the sorted copies and the BVH in place (device only, no H2D)
   if (fused) {

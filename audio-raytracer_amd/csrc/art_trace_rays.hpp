@@ -25,12 +25,22 @@ struct EchoLog {
   int keep_count;             // a later fan chunk of the frame: the counts go on
 };
 // The logging cast's margin operand for a ray (O, d) in place of |O|_1 (node_entry's om), and the cap
-// xcap on best * |d|_1 it covers: 1.05 |O|_1 + 4 |d|_1 + 0.4 xcap (replay).
+// xcap on best * |d|_1 it covers: 1.05 |O|_1 + 4 |d|_1 + the reach term (replay).
+// The reach term covers how far outside a sphere an echo blocker can be reported at reach xcap:
+// 0.4 xcap by the square-root form of the sphere lemma, or, with no sphere smaller than r_min,
+// kLogReachSq (r + xcap)^2 / r + kLogReachLin xcap at r = min(r_min, xcap) by its r-aware form
+// (sphere_report_slack, art_frame_math.hpp; (r + X)^2 / r decreases on (0, X], and beyond X the
+// sphere's own scale covers it). The linear part is sized by the boxes, whose smaller factor (1e-4)
+// has to cover the echo ray's deviation from the primary segment, 1.4e-6 xcap, with the same operand.
+// A non-finite or zero operand gives NaN or infinity there, and the fminf keeps 0.4 xcap.
+constexpr float kLogReachSq = 2e-4f, kLogReachLin = 2.8e-2f;
 __device__ __forceinline__ float log_margin_om(const DevScene& sc, vec3 O, float d1, float& xcap) {
   const CullRec root = ldc(sc.bvh, 0);
   xcap = kLogCapFrac * ((root.hix - root.lox) + (root.hiy - root.loy) + (root.hiz - root.loz));
   const float b = 1.05f * (fabsf(O.x) + fabsf(O.y) + fabsf(O.z)) + 4.0f * d1;
-  return b + 0.4f * xcap;
+  const float r = fminf(sc.r_min, xcap), rx = r + xcap;
+  const float reach = ART_SPHERE_SLACK_SCALE * (kLogReachSq * (rx * (rx / r)) + kLogReachLin * xcap);
+  return b + fminf(0.4f * xcap, reach);
 }
 
 constexpr int kLiveCounters = 32;  // per-bounce live-list counters (H <= 32)

@@ -168,6 +168,14 @@ ART_API int art_debug_last_plan(art_ctx* ctx, uint32_t* bits);
  * reports 0 and 0. Synchronizes. */
 ART_API int art_debug_echo_decided(art_ctx* ctx, uint64_t* replayed, uint64_t* traversed);
 
+/* Diagnostics (tests, ABI 3.8): the sphere lemma's bound as the margins use it. *slack is how far
+ * outside a sphere of radius r the reference's float test can report a hit for a segment that starts
+ * within D of the centre (the smaller of the square-root form and the r-aware form, DESIGN.md §5
+ * item 8). With scene_r_min non-NULL (ctx must then have a bound scene on a device), it also receives
+ * the lower bound of the sphere radii that the echo replay's margins of the next frame use (+infinity
+ * without spheres). ctx may be NULL when scene_r_min is. */
+ART_API int art_debug_sphere_slack(art_ctx* ctx, float r, float D, float* slack, float* scene_r_min);
+
 /* Context over an explicit list of HIP devices: fans of every art_schedule are sharded
  * contiguously over the list (one HIP stream, one scene copy and one set of buffers per entry).
  * An id may repeat: art_create_on({0, 0, 0}, 3, &ctx) runs the in-process multi-device split and
