@@ -66,6 +66,9 @@ def plan_names(bits: int) -> str:
 
 
 ART_KIND_SPHERE, ART_KIND_AABB, ART_KIND_OBB = 0, 1, 2
+# art_debug_bvh_records (include/art_device.h): which array, and the 32-byte record as it lies in memory
+ART_DEBUG_BVH_BOUNDS, ART_DEBUG_BVH_NODES = 0, 1
+CULL_REC = np.dtype([("lo", "<f4", 3), ("fscale", "<f4"), ("hi", "<f4", 3), ("factor", "<f4")])
 ART_OUT_HIT_RESULTS = 0x1
 # art_fan.ray_hit_ids: ColliderType (Enums/ColliderType.cs) << 30 | index in that type's array
 ART_COLLIDER_AABB, ART_COLLIDER_OBB, ART_COLLIDER_SPHERE = 1, 2, 3
@@ -235,6 +238,7 @@ SIGNATURES = {
     "art_kernel_timing": (I32, [VP, C.POINTER(art_kernel_times)]),
     "art_executed_counts": (I32, [VP, C.POINTER(art_exec_counts)]),
     "art_debug_leaf_order": (I32, [VP, C.POINTER(U32), I32]),
+    "art_debug_bvh_records": (I32, [VP, I32, C.POINTER(C.c_float), I32]),
     "art_debug_last_plan": (I32, [VP, C.POINTER(U32)]),
     "art_debug_echo_decided": (I32, [VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "art_debug_sphere_slack": (I32, [VP, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

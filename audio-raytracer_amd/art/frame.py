@@ -273,6 +273,21 @@ class Context:
             self._raise(rc)
         return buf[:rc].copy()
 
+    def debug_bvh_records(self, which: int) -> np.ndarray:
+        """The bound scene's per-collider broad-phase bounds (abi.ART_DEBUG_BVH_BOUNDS, global order) or
+        BVH nodes (abi.ART_DEBUG_BVH_NODES, heap order) as abi.CULL_REC records (art_debug_bvh_records;
+        diagnostics, synchronizes). Empty for a scene without a BVH."""
+        n = self.lib.art_debug_bvh_records(self.ptr, which, None, 0)
+        if n < 0:
+            self._raise(n)
+        buf = np.zeros(n, dtype=abi.CULL_REC)
+        if n:
+            rc = self.lib.art_debug_bvh_records(self.ptr, which, buf.ctypes.data_as(C.POINTER(C.c_float)), n)
+            if rc < 0:
+                self._raise(rc)
+            assert rc == n
+        return buf
+
     def debug_last_plan(self) -> int:
         """ART_PLAN_* bits of the launch plan the throughput raytrace stage took for the last frame
         (art_debug_last_plan; diagnostics). 0 after a reference-order or counting frame."""

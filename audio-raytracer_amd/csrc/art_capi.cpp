@@ -50,8 +50,8 @@ namespace {
 // art_dsp_tick_params_host, art_dsp_settings_bind, art_dsp_tick_params_device, art_dsp_tick_device);
 // 3.6: the listener mix (art_dsp_mix_device, art_dsp_tick_mix_device, art_dsp_mix_host); 3.7: targets
 // added and removed on a bound scene (art_targets_reserve, art_target_capacity, art_targets_last_resize,
-// art_debug_target_sync_map); 3.8: art_debug_sphere_slack
-constexpr uint32_t kAbiVersion = (3u << 16) | 8u;
+// art_debug_target_sync_map); 3.8: art_debug_sphere_slack; 3.9: art_debug_bvh_records
+constexpr uint32_t kAbiVersion = (3u << 16) | 9u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -660,6 +660,22 @@ ART_API int art_debug_leaf_order(art_ctx* c, uint32_t* out, int32_t cap) {
   HIP_TRY(c, hipDeviceSynchronize());
   if (m > 0) HIP_TRY(c, hipMemcpy(out, dv.sc.bvh_ref, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return m;
+}
+
+ART_API int art_debug_bvh_records(art_ctx* c, int32_t which, float* out, int32_t cap) {
+  static_assert(sizeof(CullRec) == 8 * sizeof(float), "CullRec: 8 floats");
+  if (!c || (!out && cap > 0) || cap < 0 || (which != ART_DEBUG_BVH_BOUNDS && which != ART_DEBUG_BVH_NODES)) return ART_E_INVALID;
+  if (c->devs.empty() || !c->devs[0].bound) return ART_E_STATE;
+  Device& dv = c->devs[0];
+  const int n = dv.sc.ns + dv.sc.na + dv.sc.no;
+  if (!dv.sc.bvh || !dv.sc.cull || n <= 0) return 0;
+  const CullRec* src = which == ART_DEBUG_BVH_BOUNDS ? dv.sc.cull : dv.sc.bvh;
+  const int count = which == ART_DEBUG_BVH_BOUNDS ? n : (int)bvh_node_count(n);
+  const int m = count < cap ? count : cap;
+  HIP_TRY(c, hipSetDevice(dv.id));
+  HIP_TRY(c, hipDeviceSynchronize());
+  if (m > 0) HIP_TRY(c, hipMemcpy(out, src, (size_t)m * sizeof(CullRec), hipMemcpyDeviceToHost));
+  return count;
 }
 
 ART_API int art_debug_last_plan(art_ctx* c, uint32_t* bits) {

@@ -142,6 +142,20 @@ ART_API int art_kernel_timing(art_ctx* ctx, art_kernel_times* out);
  * written (the bound scene's collider count when cap allows) or a negative art error. Synchronizes. */
 ART_API int art_debug_leaf_order(art_ctx* ctx, uint32_t* out, int32_t cap);
 
+/* Diagnostics (tests, ABI 3.9): the broad-phase records of the bound scene's BVH on the context's
+ * first device, as they lie in device memory: 8 floats per record (lo.xyz, fscale, hi.xyz, factor).
+ * ART_DEBUG_BVH_BOUNDS: the per-collider bounds, one record per collider in global order (spheres,
+ * AABBs, OBBs). ART_DEBUG_BVH_NODES: the tree's nodes in heap order (root 0, children of node g at
+ * 4g + 1 .. 4g + 4, the leaves last; a node without colliders is stored as lo = hi = +infinity with
+ * fscale = factor = 0). Copies at most cap records to out (out may be NULL when cap is 0) and returns
+ * the array's record count, 0 for a scene without a BVH (no colliders), or a negative art error
+ * (ART_E_STATE: no scene bound). Unlike art_debug_leaf_order, which returns the number of entries it
+ * wrote, the return value here does not depend on cap: a call with cap 0 asks for the size.
+ * Upload-bound and resident-bound scenes alike. Synchronizes. */
+#define ART_DEBUG_BVH_BOUNDS 0
+#define ART_DEBUG_BVH_NODES  1
+ART_API int art_debug_bvh_records(art_ctx* ctx, int32_t which, float* out, int32_t cap);
+
 /* Diagnostics (tests, ABI 3.2): the launch plan the throughput raytrace stage chose for the most
  * recent frame enqueued on the context's first device (art_schedule, art_launch_device), as
  * ART_PLAN_* bits. Exactly one of FUSED / HM / SPLIT / FOLD / PER_BOUNCE is set per fan chunk; a

@@ -26,7 +26,8 @@ def declared_symbols():
 def test_headers_declare_expected_surface():
     names = declared_symbols()
     for n in ("art_create", "art_schedule", "art_is_completed", "art_complete", "art_destroy", "art_last_error",
-              "art_scene_bind", "art_launch_device", "art_synth_scene", "art_debug_leaf_order", "art_debug_last_plan"):
+              "art_scene_bind", "art_launch_device", "art_synth_scene", "art_debug_leaf_order", "art_debug_last_plan",
+              "art_debug_bvh_records"):
         assert n in names
 
 
@@ -78,8 +79,8 @@ def test_header_struct_sizes_match_bindings(tmp_path):
 def test_version():
     v = art.load_library().art_version()
     # 3.0: art_kernel_times per kernel family (a grown struct: major bump); 3.1: ART_CTX_EVENT_EACH_LAUNCH,
-    # art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*
-    assert v >> 16 == 3 and (v & 0xffff) >= 2
+    # art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*; 3.9: art_debug_bvh_records
+    assert v >> 16 == 3 and (v & 0xffff) >= 9
 
 
 def test_plan_bits_match_header():
