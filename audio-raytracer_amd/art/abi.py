@@ -150,6 +150,12 @@ class art_target_resize_stats(C.Structure):  # ABI 3.7
                 ("lists_rebuilt", C.c_int32), ("lists_full_rebuild", C.c_int32), ("bytes_uploaded", C.c_uint64)]
 
 
+class art_collider_resize_stats(C.Structure):  # ABI 3.10
+    _fields_ = [("kept_bound", C.c_int32), ("added", C.c_int32), ("removed", C.c_int32), ("relabelled", C.c_int32),
+                ("bvh_rebuilt", C.c_int32), ("levels_changed", C.c_int32), ("cells_rebuilt", C.c_int32),
+                ("bytes_uploaded", C.c_uint64)]
+
+
 class art_exec_kernel(C.Structure):
     _fields_ = [("sphere", C.c_uint64), ("aabb", C.c_uint64), ("obb", C.c_uint64), ("cull_box", C.c_uint64),
                 ("cell_entries", C.c_uint64)]
@@ -266,6 +272,9 @@ SIGNATURES = {
     "art_colliders_clear": (I32, [VP]),
     "art_colliders_sync": (I32, [VP]),
     "art_colliders_last_sync": (I32, [VP, C.POINTER(art_collider_sync_stats)]),
+    "art_colliders_reserve": (I32, [VP, I32, I32, I32]),
+    "art_collider_capacity": (I32, [VP, I32]),
+    "art_colliders_last_resize": (I32, [VP, C.POINTER(art_collider_resize_stats)]),
     "art_target_add": (I32, [VP, VP, C.POINTER(I32)]),
     "art_target_set": (I32, [VP, I32, VP]),
     "art_target_set_many": (I32, [VP, VP, VP, I32]),

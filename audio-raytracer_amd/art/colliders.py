@@ -81,6 +81,21 @@ class ColliderStore:
         self._check(self.ctx.lib.art_colliders_last_sync(self.ctx.ptr, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in abi.art_collider_sync_stats._fields_}
 
+    def reserve(self, spheres: int, aabbs: int, obbs: int):
+        """Room for up to this many colliders of each kind in scenes bound from now on
+        (art_colliders_reserve): a sync that changes a count within it keeps such a scene bound.
+        0, 0, 0: a count change unbinds."""
+        self._check(self.ctx.lib.art_colliders_reserve(self.ctx.ptr, spheres, aabbs, obbs))
+
+    def capacity(self, kind: int) -> int:
+        return self._check(self.ctx.lib.art_collider_capacity(self.ctx.ptr, kind))
+
+    def last_resize(self) -> dict:
+        """What the last sync did to the lists and to a bound scene (art_collider_resize_stats)."""
+        st = abi.art_collider_resize_stats()
+        self._check(self.ctx.lib.art_colliders_last_resize(self.ctx.ptr, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in abi.art_collider_resize_stats._fields_}
+
 
 def resident_frame(frame: Frame) -> Frame:
     """A shallow copy of `frame` whose desc carries no colliders (for ART_CTX_RESIDENT_COLLIDERS)."""

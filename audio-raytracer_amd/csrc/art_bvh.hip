@@ -1005,6 +1005,173 @@ bool launch_sync_refit(const ScatterArgs& a, DevScene& sc, const SortBufs& sb, h
   return true;
 }
 
+int bvh_tree_layout(int n, int& leaf0) {
+  int total = 0;
+  leaf0 = 0;
+  return bvh_layout(n, leaf0, total);
+}
+
+// ------------------------------------------------------------------------------------------
+// Counts changed on a bound resident scene (art_colliders_sync within a reserved capacity): the
+// leaf order follows without a sort. A label is (kind rank, in-type index), bvh_ref's encoding;
+// swap-back removes shorten a kind's list from its end, so labels only vanish and appear at the
+// kinds' tails. With n old and n' new colliders:
+//   A = the appearing labels, ascending (kind rank, index); a = |A|
+//   H = the old leaf positions of the vanishing labels, ascending; h = |H| (through the old bvh_pos
+//       and the old global index)
+//   ref[H[j]] = A[j] for j < min(a, h)
+//   a > h: ref[n + (j - h)] = A[j] for j in [h, a); n' = n + a - h
+//   h > a: n' = n - (h - a); B = the unfilled holes below n', ascending; M = the positions in
+//          [n', n) that still hold a label (filled holes included), ascending; |B| = |M| and
+//          ref[B[j]] = ref[M[j]]
+//   every other position keeps its reference: ref[0..n') is a left-packed permutation of the labels
+//   bvh_pos[global'(ref[k])] = k for k < n', with the new counts
+// Any leaf order gives an exact BVH (node boxes are unions): the full refit that follows makes the
+// tree exact, and only its tightness depends on who sits where (tests/bvh_relabel_ref.py restates
+// the rule on the host).
+// One workgroup, like sync_refit_kernel: the hole bitmap lives in LDS (8 KB at kSyncRefitMax
+// positions), each lane owns a run of its words, and per-word popcounts with one block scan give
+// the rank of every hole (its index in H; B's is that minus a, M's follows from the position). The
+// old bvh_pos is dead once the holes are marked, so it carries M's references between the two
+// passes; no atomics on global memory and no other scratch.
+// ------------------------------------------------------------------------------------------
+struct RelabelCounts { int o[3], n[3]; };
+constexpr int kRelabelWords = (int)(kSyncRefitMax / 32);
+
+// Exclusive prefix of v over the workgroup's 1024 lanes, and the total.
+__device__ __forceinline__ int relabel_scan(int v, int* s_wave, int& total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int t = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(t, d);
+    if (lane >= d) t += o;
+  }
+  if (lane == 63) s_wave[w] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int k = 0; k < 16; ++k) { const int x = s_wave[k]; s_wave[k] = run; run += x; }
+    s_wave[16] = run;
+  }
+  __syncthreads();
+  const int ex = s_wave[w] + t - v;
+  total = s_wave[16];
+  __syncthreads();
+  return ex;
+}
+// A[j]
+__device__ __forceinline__ uint32_t relabel_appearing(int j, const RelabelCounts& c) {
+  for (int k = 0; k < 3; ++k) {
+    const int ak = max(0, c.n[k] - c.o[k]);
+    if (j < ak) return ((uint32_t)k << 30) | (uint32_t)(c.o[k] + j);
+    j -= ak;
+  }
+  return 0u;
+}
+// the bits of bitmap word w that stand for positions below `end`
+__device__ __forceinline__ uint32_t relabel_below(int end, int w) {
+  const int lo = w << 5;
+  return end <= lo ? 0u : (end >= lo + 32 ? ~0u : (1u << (end - lo)) - 1u);
+}
+
+__global__ __launch_bounds__(1024) void bvh_relabel_kernel(RelabelCounts c, uint32_t* ref, uint32_t* pos, uint32_t* status) {
+  __shared__ uint32_t s_hole[kRelabelWords];
+  __shared__ int s_wave[17];
+  const int tid = threadIdx.x;
+  const int n = c.o[0] + c.o[1] + c.o[2];
+  int a = 0, h = 0;
+  for (int k = 0; k < 3; ++k) { a += max(0, c.n[k] - c.o[k]); h += max(0, c.o[k] - c.n[k]); }
+  const int n2 = n + a - h;
+  const int words = (max(n, n2) + 31) >> 5;  // <= kRelabelWords (launch_bvh_relabel)
+  const int wpl = (words + 1023) >> 10;      // bitmap words per lane
+  const int w0 = min(words, tid * wpl), w1 = min(words, w0 + wpl);
+  for (int w = tid; w < words; w += 1024) s_hole[w] = 0u;
+  __syncthreads();
+  for (int v = tid; v < h; v += 1024) {  // H: the vanishing labels' positions
+    int j = v, base = 0, g = -1;
+    for (int k = 0; k < 3 && g < 0; ++k) {
+      const int hk = max(0, c.o[k] - c.n[k]);
+      if (j < hk) g = base + c.n[k] + j;
+      j -= hk;
+      base += c.o[k];
+    }
+    const uint32_t p = pos[g];
+    if (p < (uint32_t)n) atomicOr(&s_hole[p >> 5], 1u << (p & 31));
+  }
+  __syncthreads();
+  int cnt = 0, cnt_lo = 0;  // holes in this lane's words; those below n'
+  for (int w = w0; w < w1; ++w) {
+    cnt += __popc(s_hole[w]);
+    cnt_lo += __popc(s_hole[w] & relabel_below(n2, w));
+  }
+  int total = 0, hb = 0;
+  const int hbase = relabel_scan(cnt, s_wave, total);  // holes below this lane's first word
+  (void)relabel_scan(cnt_lo, s_wave, hb);              // holes below n'
+  const int ub = max(0, hb - a);                       // |B| = |M|: the unfilled holes below n'
+  int rewritten = 0;
+  int r = hbase;
+  for (int w = w0; w < w1; ++w) {
+    const uint32_t m = s_hole[w];
+    const int lo = w << 5;
+    // M: what still holds a label in [n', n) goes to the dead bvh_pos, in order
+    for (int q = max(lo, n2); q < min(lo + 32, n); ++q) {
+      const uint32_t bit = (m >> (q - lo)) & 1u;
+      const int rq = r + __popc(m & ((1u << (q - lo)) - 1u));  // holes below q
+      if (bit && rq >= a) continue;                            // an unfilled hole
+      const int jm = (q - n2) - (max(0, rq - a) - ub);
+      pos[jm] = bit ? relabel_appearing(rq, c) : ref[q];
+    }
+    for (uint32_t mm = m; mm; mm &= mm - 1u) {  // the first min(a, h) holes take A
+      const int b = __ffs((int)mm) - 1;
+      const int rr = r + __popc(m & ((1u << b) - 1u));
+      if (rr < a) {
+        ref[lo + b] = relabel_appearing(rr, c);
+        rewritten += lo + b < n2 ? 1 : 0;
+      }
+    }
+    r += __popc(m);
+  }
+  for (int j = h + tid; j < a; j += 1024) {  // a > h: the rest of A is appended
+    ref[n + j - h] = relabel_appearing(j, c);
+    ++rewritten;
+  }
+  __syncthreads();
+  r = hbase;
+  for (int w = w0; w < w1; ++w) {  // B: the unfilled holes below n' take M
+    const uint32_t full = s_hole[w];
+    const int lo = w << 5;
+    for (uint32_t mm = full & relabel_below(n2, w); mm; mm &= mm - 1u) {
+      const int b = __ffs((int)mm) - 1;
+      const int rr = r + __popc(full & ((1u << b) - 1u));
+      if (rr >= a) {
+        ref[lo + b] = pos[rr - a];
+        ++rewritten;
+      }
+    }
+    r += __popc(full);
+  }
+  __syncthreads();
+  for (int k = tid; k < n2; k += 1024) {  // bvh_pos in the new global order
+    const int g = bvh_ref_global(ref[k], c.n[0], c.n[1]);
+    if (g >= 0 && g < n2) pos[g] = (uint32_t)k;
+  }
+  (void)relabel_scan(rewritten, s_wave, total);
+  if (tid == 0 && status) *status = (uint32_t)total;
+}
+
+bool launch_bvh_relabel(const int old_n[3], const int new_n[3], const SortBufs& sb, uint32_t* status, hipStream_t st) {
+  RelabelCounts c;
+  long long n = 0, n2 = 0;
+  for (int k = 0; k < 3; ++k) {
+    c.o[k] = old_n[k]; c.n[k] = new_n[k];
+    if (old_n[k] < 0 || new_n[k] < 0) return false;
+    n += old_n[k]; n2 += new_n[k];
+  }
+  if (n <= 0 || n2 <= 0 || n > kSyncRefitMax || n2 > kSyncRefitMax || !sb.bvh_ref || !sb.bvh_pos) return false;
+  hipLaunchKernelGGL(bvh_relabel_kernel, dim3(1), dim3(1024), 0, st, c, sb.bvh_ref, sb.bvh_pos, status);
+  return true;
+}
+
 // Colliders moved but their counts did not: keep the leaf order and recompute the leaf slots and
 // node bounds in place (no sort). Bounds stay exact unions, so the culls stay exact; only their
 // tightness drifts until the next rebuild (a count change, or art_scene_bind).

@@ -50,8 +50,10 @@ namespace {
 // art_dsp_tick_params_host, art_dsp_settings_bind, art_dsp_tick_params_device, art_dsp_tick_device);
 // 3.6: the listener mix (art_dsp_mix_device, art_dsp_tick_mix_device, art_dsp_mix_host); 3.7: targets
 // added and removed on a bound scene (art_targets_reserve, art_target_capacity, art_targets_last_resize,
-// art_debug_target_sync_map); 3.8: art_debug_sphere_slack; 3.9: art_debug_bvh_records
-constexpr uint32_t kAbiVersion = (3u << 16) | 9u;
+// art_debug_target_sync_map); 3.8: art_debug_sphere_slack; 3.9: art_debug_bvh_records;
+// 3.10: colliders added and removed on a bound scene (art_colliders_reserve, art_collider_capacity,
+// art_colliders_last_resize)
+constexpr uint32_t kAbiVersion = (3u << 16) | 10u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -249,6 +251,7 @@ ART_API void art_destroy(art_ctx* c) {
     dv.raw.release(); dv.soa.release(); dv.origins.release(); dv.block.release(); dv.acc.release(); dv.counts.release();
     dv.exec.release(); dv.pairs.release(); dv.dsp.release(); dv.tick_curves.release(); dv.cones.release(); dv.tsel.release();
     dv.cell_status.release();
+    dv.relabel_status.release();
     dv.store.raw.release(); dv.store.soa.release(); dv.store.upd.release();
     if (dv.store.done) (void)hipEventDestroy(dv.store.done);
     for (hipEvent_t e : dv.store.epoch)
@@ -344,7 +347,7 @@ ART_API int art_schedule(art_ctx* c, const art_frame_desc* d, const art_fan* fan
   PhaseClock pc(&c->hp);
   Frame& f = c->fr;
   make_frame(d, hits ? ART_OUT_HIT_RESULTS : 0u, f, (c->flags & ART_CTX_RESIDENT_COLLIDERS) ? c->store.synced : nullptr,
-             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0, c->targets.reserved);
+             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0, c->targets.reserved, c->store.reserved);
   const FanLayout& L = f.L;
   const size_t origins_off = align_up(f.raw_bytes, 16);
   if (!c->h_block.reserve((size_t)fan_count * L.stride)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
@@ -521,7 +524,7 @@ ART_API int art_scene_bind(art_ctx* c, const art_frame_desc* d) {
   if (rc) return rc;
   Frame& f = c->fr;
   make_frame(d, 0u, f, (c->flags & ART_CTX_RESIDENT_COLLIDERS) ? c->store.synced : nullptr,
-             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0, c->targets.reserved);
+             (c->flags & ART_CTX_RESIDENT_TARGETS) != 0, c->targets.reserved, c->store.reserved);
   if (!c->h_in.reserve(f.raw_bytes)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
   pack_inputs(d, f, static_cast<uint8_t*>(c->h_in.p));
   count_nonowned(c, d);
@@ -548,6 +551,24 @@ ART_API int art_scene_bind(art_ctx* c, const art_frame_desc* d) {
     for (Device& dv : c->devs) {
       HIP_TRY(c, hipSetDevice(dv.id));
       if (!dv.tsel.reserve((size_t)kMaxTargets * sizeof(int))) return fail(c, ART_E_NOMEM, "device allocation failed");
+    }
+  }
+  if (f.Cc[0] + f.Cc[1] + f.Cc[2] > 0) {
+    // A later count-changing collider sync allocates nothing while it uploads at most
+    // min(capacity, kSyncRefitMax) records: every slot of the pinned image ring and the devices'
+    // copy of it at that image's size ([indices][records] per kind, 16-B aligned sections), and the
+    // word the relabel kernel reports through.
+    const size_t recs = (size_t)std::min<long long>(f.ccap(), kSyncRefitMax);
+    const size_t image = recs * (4 + sizeof(art_obb)) + 6 * 16;
+    for (HostBuf& b : c->store.h_upd)
+      if (!b.reserve(image)) return fail(c, ART_E_NOMEM, "pinned allocation failed");
+    for (Device& dv : c->devs) {
+      HIP_TRY(c, hipSetDevice(dv.id));
+      if (!dv.store.upd.reserve(image)) return fail(c, ART_E_NOMEM, "device allocation failed");
+      if (!dv.relabel_status.p) {
+        if (!dv.relabel_status.reserve(sizeof(uint32_t))) return fail(c, ART_E_NOMEM, "pinned allocation failed");
+        memset(dv.relabel_status.p, 0, sizeof(uint32_t));
+      }
     }
   }
   return ART_OK;

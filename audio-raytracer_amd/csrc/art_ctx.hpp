@@ -74,6 +74,12 @@ struct Frame {
   int Tc = 0;
   int tcap() const { return Tc > 0 ? Tc : T; }
   int ns = 0, na = 0, no = 0;
+  // Collider capacity per kind of a resident scene bound after art_colliders_reserve (each >= the
+  // kind's count): everything carve_sort and carve_cells size by collider count is sized by their
+  // sum, and a collider sync whose counts stay within them keeps the scene bound. All 0: nothing
+  // reserved (sized by the counts, a count change unbinds).
+  int Cc[3] = {0, 0, 0};
+  int ccap() const { return Cc[0] + Cc[1] + Cc[2] > 0 ? Cc[0] + Cc[1] + Cc[2] : ns + na + no; }
   uint32_t stages = 0;
   bool resident = false;               // colliders come from the resident store (art_colliders.h)
   bool res_targets = false;            // target positions and T come from the last art_targets_sync
@@ -141,9 +147,10 @@ struct SortedCache {
   uint64_t gen = ~0ull;
   const void* soa = nullptr;
   int n[3] = {-1, -1, -1};
+  int ccap = -1;  // the collider capacity the sorted copies' buffers were carved for (Frame::ccap)
   DevScene sc{};
   bool matches(const Frame& f, const void* soa_p) const {
-    return f.resident && gen != ~0ull && soa == soa_p && n[0] == f.ns && n[1] == f.na && n[2] == f.no;
+    return f.resident && gen != ~0ull && soa == soa_p && n[0] == f.ns && n[1] == f.na && n[2] == f.no && ccap == f.ccap();
   }
 };
 
@@ -156,6 +163,7 @@ struct Device {
   DevBuf cones; // the cell cone table (art_cells.hip), uploaded once
   CellBufs cb{};  // muffle candidate list buffers of the current scene (upload_scene)
   DevBuf tsel;    // the moved targets of the last art_targets_sync (the partial list build's selection)
+  HostBuf relabel_status;  // pinned: leaf positions the last bvh_relabel_kernel rewrote (art_collider_resize_stats::relabelled)
   HostBuf cell_status;  // pinned (tail, dropped) of the cell lists' entry arena, written by the device (CellBufs::status)
   bool cells_partial = false;  // a target's lists were rebuilt on their own since the last full build: the arena holds garbage
   DevBuf pairs; // global visibility pairs of the split raytrace path
@@ -206,6 +214,12 @@ struct ColliderStore {
   std::vector<int16_t> synced_tid[3];
   std::vector<int> tid_hist[3];
   art_collider_sync_stats last_sync{};
+  int reserved[3] = {0, 0, 0};   // art_colliders_reserve
+  art_collider_resize_stats last_resize{};
+  bool relabel_pending = false;  // last_resize.relabelled is still to be read from device 0's relabel_status
+  // adds and effective removes since the bound scene's last kd build (the synced ones), and those
+  // since the last sync: a relabelled tree loses tightness with them (art_store.cpp, kResortDen)
+  long long churn = 0, churn_unsynced = 0;
   std::vector<uint8_t> cpu_recs[3];  // CPU backend: the records at the last sync
   // pinned update images of art_colliders_sync, a ring (sync s uses slot s % kUpdRing): a slot is
   // reused only after the previous epoch's syncs are done (one event per epoch, not per sync)
@@ -301,7 +315,7 @@ int fail(art_ctx* c, int code, const char* fmt, ...) __attribute__((format(print
 int validate_desc(art_ctx* c, const art_frame_desc* d);
 FanLayout make_layout(const art_frame_desc* d, uint32_t out_flags);
 void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts = nullptr,
-                bool resident_targets = false, int target_capacity = 0);
+                bool resident_targets = false, int target_capacity = 0, const int* collider_capacity = nullptr);
 // True when the permeation slot table of f (Frame::slot_batch) is the same for T targets.
 bool slot_tables_hold(const Frame& f, int T);
 void pack_inputs(const art_frame_desc* d, const Frame& f, uint8_t* h);

@@ -152,7 +152,7 @@ bool slot_tables_hold(const Frame& f, int T) {
 }
 
 void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int* resident_counts, bool resident_targets,
-                int target_capacity) {
+                int target_capacity, const int* collider_capacity) {
   // the direction-coherent order of the last frame is kept while its directions stay the same
   // (they are set once at init, AudioRayTracer.cs:72-86): a 3-KB compare instead of the sort
   std::vector<int> last_order;
@@ -168,6 +168,8 @@ void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int
   if (resident_counts) {
     f.resident = true;
     f.ns = resident_counts[0]; f.na = resident_counts[1]; f.no = resident_counts[2];
+    if (collider_capacity && collider_capacity[0] + collider_capacity[1] + collider_capacity[2] > 0)
+      for (int k = 0; k < 3; ++k) f.Cc[k] = std::max(collider_capacity[k], resident_counts[k]);
   }
   // collider sections of the staging buffer (empty when the store holds them)
   const size_t sn = f.resident ? 0 : (size_t)f.ns, an = f.resident ? 0 : (size_t)f.na, on = f.resident ? 0 : (size_t)f.no;
@@ -227,8 +229,8 @@ void make_frame(const art_frame_desc* d, uint32_t out_flags, Frame& f, const int
   f.off_reset = o; o = align_up(o + (size_t)f.TC, 16);
   f.off_order = o; o = align_up(o + (size_t)f.R * 4, 16);
   f.raw_bytes = o;
-  // (by the target capacity: whether the scene has lists, and their room, hold for every count it takes)
-  f.cells_cap = (uint32_t)cells_entry_cap(f.tcap(), f.ns + f.na + f.no, f.res_targets);
+  // (by the target and collider capacities: whether the scene has lists, and their room, hold for every count it takes)
+  f.cells_cap = (uint32_t)cells_entry_cap(f.tcap(), f.ccap(), f.res_targets);
   Carver sizes{0};
   carve_decoded(sizes, f);
   carve_sort(sizes, f);
@@ -250,7 +252,7 @@ DecodedColliders carve_decoded(Carver& c, const Frame& f) {
 }
 
 SortBufs carve_sort(Carver& c, const Frame& f) {
-  const int ni = f.ns + f.na + f.no;
+  const int ni = f.ccap();  // (the counts' sum, or the reserved capacity they may grow to)
   const size_t n = (size_t)ni;
   SortBufs sb;
   sb.temp_bytes = sort_scene_temp_bytes(ni);
@@ -287,7 +289,7 @@ CellBufs carve_cells(Carver& c, const Frame& f) {
   cb.box = c.take<CullRec>(sizeof(CullRec));
   cb.tail = c.take<uint32_t>(2 * sizeof(uint32_t));
   cb.ent = c.take<uint2>((size_t)cb.cap * 8);
-  cb.geo = c.take<void>(cells_geo_bytes((int)T, f.ns + f.na + f.no));
+  cb.geo = c.take<void>(cells_geo_bytes((int)T, f.ccap()));
   return cb;
 }
 

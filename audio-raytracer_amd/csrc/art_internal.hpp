@@ -209,6 +209,14 @@ int launch_build_bvh(DevScene& sc, const SortBufs& sb, hipStream_t st);
 // Colliders moved, counts unchanged: recompute the sorted copies' records, chunk bounds and the
 // BVH's bounds and leaf slots in place, keeping every order.
 int launch_refit_scene(DevScene& sc, const SortBufs& sb, hipStream_t st);
+// Levels of the tree over n colliders (0: none) and its first leaf node (DevScene::bvh_levels, bvh_leaf0).
+int bvh_tree_layout(int n, int& leaf0);
+// Counts changed within a reserved capacity (old_n -> new_n per kind, both totals in
+// [1, kSyncRefitMax]): bvh_ref and bvh_pos rewritten in place by the relabel rule (art_bvh.hip,
+// bvh_relabel_kernel), one workgroup; *status (device-visible, may be pinned host memory or NULL) =
+// the leaf positions below the new count whose reference was written. The caller then sets the
+// scene's counts and layout and runs launch_refit_scene. false: nothing launched.
+bool launch_bvh_relabel(const int old_n[3], const int new_n[3], const SortBufs& sb, uint32_t* status, hipStream_t st);
 
 // Muffle candidate lists (art_cells.hip): built after every scene upload / refit on stream st.
 // Sort key of a cell entry's near bound (bits of a float): the top 16 bits of its non-negative

@@ -117,10 +117,13 @@ static int build_bvh(art_ctx* c, Device& dv, const Frame& f, bool reuse) {
       return fail(c, ART_E_DEVICE, "collider refit failed");
   } else if (launch_sort_scene(sc, dv.sb, dv.stream) != 0) {
     return fail(c, ART_E_DEVICE, "collider sort failed");
+  } else if (f.resident) {
+    c->store.churn = 0;  // a fresh kd order of the synced colliders
   }
   dv.sorted.gen = f.resident ? c->store.sync_gen : ~0ull;
   dv.sorted.soa = dv.soa.p;
   dv.sorted.n[0] = f.ns; dv.sorted.n[1] = f.na; dv.sorted.n[2] = f.no;
+  dv.sorted.ccap = f.ccap();
   return ART_OK;
 }
 
@@ -189,7 +192,9 @@ int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in) {
   if (rc == 0) {
     cb.cones = static_cast<const CellCone*>(dv.cones.p);
     cb.alpha_max = cone_table().alpha_max;
-    cb.compact = (ART_CELLS_COMPACT && f.ns < (1 << 16) && f.na < (1 << 16) && f.no < (1 << 16)) ? 1u : 0u;  // 4-B entries
+    // 4-B entries (by the kinds' capacities: the entry format holds for every count the scene can take)
+    cb.compact = (ART_CELLS_COMPACT && std::max(f.ns, f.Cc[0]) < (1 << 16) && std::max(f.na, f.Cc[1]) < (1 << 16) &&
+                  std::max(f.no, f.Cc[2]) < (1 << 16)) ? 1u : 0u;
     cb.status = static_cast<uint32_t*>(status);
     dv.cb = cb;
     if (launch_build_cells(sc, dv.cb, cells_st) != 0) rc = fail(c, ART_E_DEVICE, "muffle cell lists failed");

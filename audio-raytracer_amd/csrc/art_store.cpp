@@ -4,6 +4,8 @@
 // plan_target_sync) and four steps (stage_image, sync_device per device, commit_sync; the target
 // half's are stage_target_image, sync_device_targets, commit_target_sync). Both kinds of sync
 // share the ring of pinned update images and its epoch events.
+#include <cstdlib>
+
 #include "art_ctx.hpp"
 
 using namespace art;
@@ -65,7 +67,31 @@ struct SyncPlan {
   int nd;                     // dirty records over the kinds
   bool cells_ok;              // every changed collider stayed within the muffle cell lists' slack
   RingSlot ring;              // the image's slot in the pinned ring
+  // A count change that every device's bound resident scene follows in place (the scene was bound
+  // with a collider capacity, every kind stays within it and no device list has to grow): the
+  // labels that appear and vanish at the kinds' tails, and whether the leaf order is relabelled
+  // (bvh_relabel_kernel) or sorted again in the same buffers.
+  int old_n[3];               // the counts of the last sync
+  int added, removed;
+  bool resize;
+  bool rebuild;               // (of a resize) the full kd build instead of the relabel
 };
+
+// A relabelled tree loses tightness: survivors that a swap-back moved and new colliders sit where a
+// stranger was. Once the adds and effective removes since the last kd build exceed 1 / kResortDen of
+// the colliders, the count-changing sync sorts again in place; 1 = at every count change, 0 = never.
+// Measured at config 2 (profiles/collider_churn.txt): 64 churned colliders of 4096
+// already take the static frame from 0.092 to 0.319 ms, no fraction down to 1/64 stays within the
+// measurement spread of a fresh bind, and the step that sorts every time is the fastest against the
+// rebind it replaces. So the default sorts at every count change, and the relabel is what
+// ART_BVH_RESORT_DEN in the environment (read per sync) asks for.
+constexpr int kResortDen = 1;
+int resort_den() {
+  const char* e = getenv("ART_BVH_RESORT_DEN");
+  if (!e || !*e) return kResortDen;
+  const long v = strtol(e, nullptr, 10);
+  return v < 0 ? kResortDen : (int)std::min<long>(v, 1 << 30);
+}
 
 // No HIP call, but it does change host state: it grows the devices' capacities (x2) and marks them
 // fresh (sync_device then frees and reallocates their buffers), and it takes the sync's generation
@@ -79,11 +105,35 @@ SyncPlan plan_sync(art_ctx& c) {
   p.fresh = false;
   for (Device& dv : c.devs) {  // a list outgrew the device capacity: everything is uploaded again
     StoreDev& d = dv.store;
-    if (p.n[0] > d.cap[0] || p.n[1] > d.cap[1] || p.n[2] > d.cap[2] || !d.raw.p) {
-      for (int k = 0; k < 3; ++k) d.cap[k] = std::max({p.n[k], 2 * d.cap[k], 64});
+    // (a reserved capacity the lists do not have yet is taken now unless a bound scene reads them)
+    const bool reserve_grows = !dv.bound && (s.reserved[0] > d.cap[0] || s.reserved[1] > d.cap[1] || s.reserved[2] > d.cap[2]);
+    if (p.n[0] > d.cap[0] || p.n[1] > d.cap[1] || p.n[2] > d.cap[2] || !d.raw.p || reserve_grows) {
+      for (int k = 0; k < 3; ++k) d.cap[k] = std::max({p.n[k], 2 * d.cap[k], 64, s.reserved[k]});
       d.fresh = true;
     }
     p.fresh |= d.fresh;
+  }
+  // the labels (kind, index) that appear and vanish: only at the kinds' tails (swap-back removes)
+  p.added = p.removed = 0;
+  for (int k = 0; k < 3; ++k) {
+    p.old_n[k] = s.store_synced ? s.synced[k] : 0;
+    p.added += std::max(0, p.n[k] - p.old_n[k]);
+    p.removed += std::max(0, p.old_n[k] - p.n[k]);
+  }
+  s.churn += s.churn_unsynced;
+  s.churn_unsynced = 0;
+  const Frame& f = c.fr;
+  p.resize = !c.cpu && p.counts_changed && s.store_synced && !p.fresh && f.resident && f.Cc[0] + f.Cc[1] + f.Cc[2] > 0 &&
+             !c.devs.empty();
+  for (int k = 0; p.resize && k < 3; ++k) p.resize = p.n[k] <= f.Cc[k];
+  for (const Device& dv : c.devs)
+    p.resize = p.resize && dv.bound && dv.sc.ns == p.old_n[0] && dv.sc.na == p.old_n[1] && dv.sc.no == p.old_n[2];
+  p.rebuild = false;
+  if (p.resize) {
+    const long long n_old = (long long)p.old_n[0] + p.old_n[1] + p.old_n[2], n_new = (long long)p.n[0] + p.n[1] + p.n[2];
+    const int den = resort_den();
+    p.rebuild = n_old == 0 || n_new == 0 || f.ccap() > kSyncRefitMax || den == 1 || (den > 1 && s.churn > n_new / den);
+    if (p.rebuild) s.churn = 0;
   }
   p.bytes = 0;
   for (int k = 0; k < 3; ++k) {
@@ -180,7 +230,7 @@ struct EpochMark {
 // One device's share of a sync, async on the stream it picks: scatter + decode of the dirty records
 // (or the full decode after a count change), the bound resident scene's refit and, outside the
 // slack, its cell lists.
-int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt) {
+int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt, art_collider_resize_stats& rs) {
   StoreDev& s = dv.store;
   HIP_TRY(c, hipSetDevice(dv.id));
   if (s.fresh) { s.raw.release(); s.soa.release(); }  // grown capacity: new buffers, every record uploaded
@@ -205,6 +255,7 @@ int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt) 
   // moved colliders of a bound resident scene: one launch scatters the records from the pinned image
   // and refits the BVH (launch_sync_refit), below
   const bool refit_follows = p.nd && dv.bound && c->fr.resident && !p.counts_changed;
+  const bool resize = p.resize && dv.bound && c->fr.resident;  // (the same for every device: plan_sync)
   const bool fused = refit_follows && (long long)p.n[0] + p.n[1] + p.n[2] <= kSyncRefitMax && dv.sc.bvh_levels > 0 && dv.sb.bvh;
   if (p.nd && !fused) {
     HIP_TRY(c, hipMemcpyAsync(s.upd.p, h, p.bytes, hipMemcpyHostToDevice, ss));
@@ -222,11 +273,63 @@ int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt) 
   // another stream waits on that stream's fence, work on dv.stream on it through LaunchFence::wait.
   if (!s.done) HIP_TRY(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
   const bool lazy = ss != dv.stream;
-  if (!refit_follows && !lazy) HIP_TRY(c, hipEventRecord(s.done, ss));
+  if (!refit_follows && !resize && !lazy) HIP_TRY(c, hipEventRecord(s.done, ss));
   s.dec = v.dec;
   for (int k = 0; k < 3; ++k) s.n[k] = p.n[k];
   s.fresh = false;
   if (!(dv.bound && c->fr.resident)) return epoch.record(c);
+  if (resize) {
+    // A count change within the scene's capacity, in its buffers and in stream order: the leaf order
+    // follows the labels that vanished and appeared (or is sorted again), the full refit rewrites
+    // every leaf slot (the empty ones up to the new leaf count, the slot stride when the first OBB
+    // appears or the last one leaves) and every node (a level change needs nothing more), and the
+    // cell lists are built for the new records. Nothing is allocated.
+    if (!dv.relabel_status.p) {  // (a scene bound by art_schedule: art_scene_bind has it already)
+      if (!dv.relabel_status.reserve(sizeof(uint32_t))) return fail(c, ART_E_NOMEM, "pinned allocation failed");
+      memset(dv.relabel_status.p, 0, sizeof(uint32_t));
+    }
+    const int levels_before = dv.sc.bvh_levels;
+    const bool rebuild = p.rebuild || dv.sc.bvh_levels == 0 || !dv.sb.bvh;
+    set_colliders(dv.sc, v.dec, p.n);
+    dv.sc.r_min = c->store.sphere_rmin;
+    // Beside a kd build the lists build on the side stream, as at a bind (they need the decoded
+    // records and the targets, not the tree; the sort's surface-area passes occupy a few CUs).
+    hipStream_t cells_st = ss;
+    if (rebuild && dv.cb.cap > 0 && p.n[0] + p.n[1] + p.n[2] > 0) {
+      if (int rc = ensure_side(c, dv.side)) return rc;
+      HIP_TRY(c, hipEventRecord(dv.side.fork, ss));
+      HIP_TRY(c, hipStreamWaitEvent(dv.side.st, dv.side.fork, 0));
+      cells_st = dv.side.st;
+    }
+    if (rebuild) {
+      if (launch_build_bvh(dv.sc, dv.sb, ss) != 0) return fail(c, ART_E_DEVICE, "collider sort failed");
+    } else {
+      void* status = nullptr;
+      HIP_TRY(c, hipHostGetDevicePointer(&status, dv.relabel_status.p, 0));
+      if (!launch_bvh_relabel(p.old_n, p.n, dv.sb, static_cast<uint32_t*>(status), ss))
+        return fail(c, ART_E_DEVICE, "collider relabel not applicable");
+      HIP_TRY(c, hipGetLastError());
+      dv.sc.bvh_levels = bvh_tree_layout(p.n[0] + p.n[1] + p.n[2], dv.sc.bvh_leaf0);
+      if (launch_refit_scene(dv.sc, dv.sb, ss) != 0) return fail(c, ART_E_DEVICE, "collider refit failed");
+    }
+    HIP_TRY(c, hipGetLastError());
+    rs.bvh_rebuilt = rebuild ? 1 : 0;
+    rs.levels_changed |= dv.sc.bvh_levels != levels_before ? 1 : 0;
+    const int cells_rc = launch_build_cells(dv.sc, dv.cb, cells_st);
+    if (cells_st != ss) {  // the frames that follow on ss wait for the lists (also after a failed launch)
+      HIP_TRY(c, hipEventRecord(dv.side.join, cells_st));
+      HIP_TRY(c, hipStreamWaitEvent(ss, dv.side.join, 0));
+    }
+    if (cells_rc != 0) return fail(c, ART_E_DEVICE, "muffle cell lists failed");
+    dv.cells_partial = false;
+    cells_rebuilt = true;
+    dv.last.valid = false;
+    for (int k = 0; k < 3; ++k) dv.sorted.n[k] = p.n[k];
+    if (dv.sorted.gen != ~0ull) dv.sorted.gen = c->store.sync_gen;
+    dv.sorted.sc = dv.sc;
+    if (!lazy) HIP_TRY(c, hipEventRecord(s.done, ss));
+    return epoch.record(c);
+  }
   if (p.counts_changed) {
     dv.bound = false;  // the sorted copies are sized by count: bind again
     return epoch.record(c);
@@ -257,7 +360,7 @@ int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt) 
 
 // The host bookkeeping of a sync that every device took: dirty marks, counts, the audio_target_id
 // histograms, the cell lists' base records, the CPU backend's snapshot and the statistics.
-void commit_sync(art_ctx* c, const SyncPlan& p, bool cells_rebuilt) {
+void commit_sync(art_ctx* c, const SyncPlan& p, bool cells_rebuilt, art_collider_resize_stats rs) {
   ColliderStore& s = c->store;
   const int* n = p.n;
   if (c->fr.resident) { c->fr.ns = n[0]; c->fr.na = n[1]; c->fr.no = n[2]; }
@@ -293,6 +396,24 @@ void commit_sync(art_ctx* c, const SyncPlan& p, bool cells_rebuilt) {
   s.last_sync.reallocated = p.fresh ? 1 : 0;
   s.last_sync.cells_rebuilt = cells_rebuilt ? 1 : 0;
   s.last_sync.bytes_uploaded = p.nd ? p.bytes : 0;
+  bool is_bound = !c->devs.empty();
+  for (const Device& dv : c->devs) is_bound &= dv.bound;
+  rs.kept_bound = (p.resize && is_bound) ? 1 : 0;
+  rs.added = p.added;
+  rs.removed = p.removed;
+  rs.relabelled = 0;  // (of a relabel: read back by art_colliders_last_resize)
+  rs.cells_rebuilt = cells_rebuilt ? 1 : 0;
+  rs.bytes_uploaded = s.last_sync.bytes_uploaded;
+  s.relabel_pending = rs.kept_bound && !rs.bvh_rebuilt;
+  s.last_resize = rs;
+  if (rs.kept_bound) {  // counting frames: the colliders not owned, summed over the targets (count_nonowned)
+    c->nonowned.assign(3, 0);
+    for (int k = 0; k < 3; ++k) {
+      uint64_t owned = 0;
+      for (int t = 0; t < c->fr.T && t < 32768; ++t) owned += (uint64_t)s.tid_hist[k][(size_t)t + 32768];
+      c->nonowned[(size_t)k] = (uint64_t)c->fr.T * (uint64_t)n[k] - owned;
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------- target half
@@ -670,6 +791,7 @@ ART_API int art_collider_add(art_ctx* c, int32_t kind, const void* rec, int32_t*
   K.dirty_list.push_back(K.count);
   if (out_id) *out_id = K.count;  // AudioColliderId = NextBatch.Length before the add
   K.count++;
+  c->store.churn_unsynced++;
   return ART_OK;
 }
 
@@ -716,6 +838,7 @@ ART_API int art_collider_remove_swapback(art_ctx* c, int32_t kind, int32_t id) {
   K.count = last;
   K.recs.resize((size_t)last * rs);
   K.dirty.resize((size_t)last);
+  c->store.churn_unsynced++;
   return ART_OK;
 }
 
@@ -757,9 +880,41 @@ ART_API int art_colliders_sync(art_ctx* c) {
   const SyncPlan p = plan_sync(*c);
   if (int rc = stage_image(c, p)) return rc;
   bool cells_rebuilt = false;
+  art_collider_resize_stats rs{};
   for (Device& dv : c->devs)
-    if (int rc = sync_device(c, dv, p, cells_rebuilt)) return rc;
-  commit_sync(c, p, cells_rebuilt);
+    if (int rc = sync_device(c, dv, p, cells_rebuilt, rs)) return rc;
+  commit_sync(c, p, cells_rebuilt, rs);
+  return ART_OK;
+}
+
+ART_API int art_colliders_reserve(art_ctx* c, int32_t spheres, int32_t aabbs, int32_t obbs) {
+  if (!c) return ART_E_INVALID;
+  if (spheres < 0 || aabbs < 0 || obbs < 0) return fail(c, ART_E_INVALID, "art_colliders_reserve: negative capacity");
+  if ((long long)spheres + aabbs + obbs > kMaxColliders)
+    return fail(c, ART_E_UNSUPPORTED, "art_colliders_reserve: capacity > %lld in total", kMaxColliders);
+  if (c->inflight) return fail(c, ART_E_STATE, "art_colliders_reserve: a frame is in flight (reserve after art_complete)");
+  c->store.reserved[0] = spheres; c->store.reserved[1] = aabbs; c->store.reserved[2] = obbs;
+  return ART_OK;
+}
+
+ART_API int art_collider_capacity(art_ctx* c, int32_t kind) {
+  if (!c) return ART_E_INVALID;
+  if (kind < 0 || kind > 2) return fail(c, ART_E_INVALID, "art_collider_capacity: bad kind");
+  return c->store.reserved[kind];
+}
+
+ART_API int art_colliders_last_resize(art_ctx* c, art_collider_resize_stats* out) {
+  if (!c || !out) return ART_E_INVALID;
+  ColliderStore& s = c->store;
+  if (s.relabel_pending && !c->devs.empty() && c->devs[0].relabel_status.p) {
+    // the relabel kernel's own count, once (waits for that sync's work on the stream it ran on)
+    Device& dv = c->devs[0];
+    HIP_TRY(c, hipSetDevice(dv.id));
+    HIP_TRY(c, hipStreamSynchronize(dv.store.stream));
+    s.last_resize.relabelled = (int32_t)*static_cast<const volatile uint32_t*>(dv.relabel_status.p);
+    s.relabel_pending = false;
+  }
+  *out = s.last_resize;
   return ART_OK;
 }
 

@@ -87,7 +87,10 @@ ART_API int art_colliders_clear(art_ctx* ctx);
 /* UpdateJobBatch for the three kinds: publish the mirror to every device of the context.
  * Stream-ordered, not synchronous: the dirty records' upload and decode are enqueued on the
  * context's stream ahead of the next frame (art_launch_device on another stream waits for them).
- * ART_E_STATE while a frame is in flight (the reference syncs after Complete). */
+ * ART_E_STATE while a frame is in flight (the reference syncs after Complete). A count change
+ * (add, remove, clear) unbinds a bound resident scene (the BVH's buffers are sized by the counts:
+ * the next art_scene_bind / art_schedule builds them again) unless the scene was bound with a
+ * reserved capacity (art_colliders_reserve, below) and every kind stays within it. */
 ART_API int art_colliders_sync(art_ctx* ctx);
 
 /* What the last art_colliders_sync moved. */
@@ -100,6 +103,48 @@ typedef struct {
 } art_collider_sync_stats;
 
 ART_API int art_colliders_last_sync(art_ctx* ctx, art_collider_sync_stats* out);
+
+/* ------------------------------------------ colliders that appear and disappear (ABI 3.10) */
+
+/* Room for up to `spheres`, `aabbs` and `obbs` colliders of each kind in scenes bound from now on
+ * with ART_CTX_RESIDENT_COLLIDERS: a later art_colliders_sync that changes a count and keeps every
+ * kind within its capacity keeps such a scene bound. The sync stays stream-ordered like a move and
+ * allocates nothing (the store's lists, the BVH's buffers and the muffle cell lists are sized by the
+ * capacity; the update image of up to min(total capacity, 2^16) records is allocated at the bind).
+ * On the device the BVH's leaf order is sorted again in the scene's buffers, every node box is
+ * recomputed and the cell lists are rebuilt: results are those of a fresh bind. With
+ * ART_BVH_RESORT_DEN=d in the environment (scenes of up to 2^16 colliders) the sort runs only once
+ * the adds and removes since the last one exceed 1/d of the colliders (0: never; the default is 1:
+ * at every count change, the measured optimum, DESIGN.md §3b "Colliders that appear and
+ * disappear"); in between, the labels (kind, index) that vanished leave their leaf positions to
+ * the labels that appeared (RemoveAtSwapBack shortens a list from its end, so labels change only at
+ * the tails; a survivor swapped into a hole is a changed record at an existing label) and the tail
+ * of the leaf order is packed: any leaf order gives an exact BVH, only its tightness suffers.
+ * A scene bound with more colliders of a kind than reserved is sized by its own count, and that
+ * count is the kind's capacity. 0, 0, 0 (the default) = a count change unbinds, as before. Does not
+ * touch a scene that is already bound. Reserve before the store's first sync: a store whose device
+ * lists have to grow past their allocation unbinds once more.
+ * Whether a scene has muffle cell lists, and their room, is decided from the capacity (and the
+ * target capacity): a scene has lists for every count it can take, or for none.
+ * ART_E_INVALID for a negative capacity, ART_E_UNSUPPORTED above the collider limit (2^24) in total,
+ * ART_E_STATE while a frame is in flight.
+ * Nothing new stays with the caller: the fan layout does not depend on the collider counts. */
+ART_API int art_colliders_reserve(art_ctx* ctx, int32_t spheres, int32_t aabbs, int32_t obbs);
+ART_API int art_collider_capacity(art_ctx* ctx, int32_t kind);   /* reserved capacity of the kind, or < 0 */
+
+/* What the last art_colliders_sync did to the lists and to a bound scene (the CPU backend, which
+ * keeps no device scene, reports kept_bound 0 and the counts). */
+typedef struct {
+    int32_t kept_bound;     /* 1: the bound scene followed the count change */
+    int32_t added, removed; /* labels that appeared / vanished, all kinds */
+    int32_t relabelled;     /* leaf positions whose reference was rewritten by the relabel kernel (read
+                               back from device 0: art_colliders_last_resize waits for that sync) */
+    int32_t bvh_rebuilt;    /* 1: the full kd build ran in place (the default; churn threshold, large scene, from/to empty) */
+    int32_t levels_changed; /* 1: the tree's level count changed */
+    int32_t cells_rebuilt;
+    uint64_t bytes_uploaded;
+} art_collider_resize_stats;
+ART_API int art_colliders_last_resize(art_ctx* ctx, art_collider_resize_stats* out);
 
 /* ------------------------------------------------------------------ audio targets (ABI 3.4) */
 
