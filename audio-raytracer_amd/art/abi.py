@@ -248,6 +248,8 @@ SIGNATURES = {
     "art_debug_last_plan": (I32, [VP, C.POINTER(U32)]),
     "art_debug_echo_decided": (I32, [VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "art_debug_sphere_slack": (I32, [VP, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "art_debug_node_margin_cap": (I32, [VP, C.c_float, C.c_float, C.c_float, I32, C.c_float, C.POINTER(C.c_float),
+                                        C.POINTER(C.c_float)]),
     # art_dsp.h
     "art_dsp_process": (I32, [VP, C.POINTER(art_spatializer_settings), C.POINTER(art_audio_source), I32, I32]),
     "art_dsp_source_params_get": (I32, [C.POINTER(art_spatializer_settings), C.POINTER(art_audio_source), I32,

@@ -316,6 +316,16 @@ class Context:
             self._raise(rc)
         return float(r_min.value)
 
+    def debug_scene_s_root(self) -> float:
+        """The bound scene's sum over the axes of max(|lo|, |hi|) of the BVH root box, as the next frame's
+        node margin caps read it (art_debug_node_margin_cap; diagnostics, synchronizes)."""
+        cap, s_root = C.c_float(), C.c_float()
+        rc = self.lib.art_debug_node_margin_cap(self.ptr, C.c_float(1.0), C.c_float(1.0), C.c_float(0.0), 0, C.c_float(0.0),
+                                                C.byref(cap), C.byref(s_root))
+        if rc:
+            self._raise(rc)
+        return float(s_root.value)
+
     def launch_device(self, d_origins: int, fan_count: int, d_block: int, out_flags: int = 0, stream: int | None = None):
         rc = self.lib.art_launch_device(self.ptr, d_origins, fan_count, d_block, out_flags, stream)
         if rc:

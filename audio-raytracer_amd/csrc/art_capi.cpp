@@ -52,8 +52,8 @@ namespace {
 // added and removed on a bound scene (art_targets_reserve, art_target_capacity, art_targets_last_resize,
 // art_debug_target_sync_map); 3.8: art_debug_sphere_slack; 3.9: art_debug_bvh_records;
 // 3.10: colliders added and removed on a bound scene (art_colliders_reserve, art_collider_capacity,
-// art_colliders_last_resize)
-constexpr uint32_t kAbiVersion = (3u << 16) | 10u;
+// art_colliders_last_resize); 3.11: art_debug_node_margin_cap
+constexpr uint32_t kAbiVersion = (3u << 16) | 11u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -731,6 +731,24 @@ ART_API int art_debug_sphere_slack(art_ctx* c, float r, float D, float* slack, f
   if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) keeps no device scene", __func__);
   if (c->devs.empty() || !c->devs[0].bound) return fail(c, ART_E_STATE, "no scene bound (art_scene_bind)");
   *scene_r_min = c->devs[0].sc.r_min;
+  return ART_OK;
+}
+
+ART_API int art_debug_node_margin_cap(art_ctx* c, float r_min, float s_root, float om, int32_t has_obb, float reach, float* cap,
+                                      float* scene_s_root) {
+  if (!cap || (scene_s_root && !c)) return ART_E_INVALID;
+  *cap = art::node_margin_cap(r_min, s_root, om, has_obb != 0, reach);
+  if (!scene_s_root) return ART_OK;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) keeps no device scene", __func__);
+  if (c->devs.empty() || !c->devs[0].bound) return fail(c, ART_E_STATE, "no scene bound (art_scene_bind)");
+  Device& dv = c->devs[0];
+  *scene_s_root = 0.0f;
+  if (!dv.sc.bvh || dv.sc.ns + dv.sc.na + dv.sc.no <= 0) return ART_OK;
+  CullRec root;
+  HIP_TRY(c, hipSetDevice(dv.id));
+  HIP_TRY(c, hipDeviceSynchronize());
+  HIP_TRY(c, hipMemcpy(&root, dv.sc.bvh, sizeof root, hipMemcpyDeviceToHost));
+  *scene_s_root = art::node_abs_sum(root.lox, root.loy, root.loz, root.hix, root.hiy, root.hiz);
   return ART_OK;
 }
 

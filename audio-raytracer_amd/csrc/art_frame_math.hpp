@@ -60,6 +60,60 @@ ART_HD float sphere_report_slack(float r, float D) {
   return fminf(root, lin);
 }
 
+// Per-ray cap of a BVH node's margin (the capped node margin). A node that holds a
+// sphere carries kCullSphere * (scale + om), the square-root form of the lemma above at the node's own
+// scale; the r-aware form at the scene's smallest radius needs far less once r_min is not tiny. For a
+// ray whose margin operand is om, every collider centre lies within D = s_root + om of the ray's start,
+// s_root = node_abs_sum of the BVH root's stored box (it bounds |c|_1 + r and |c|_1 + |h|_1 of every
+// collider). The cap is the larger of
+//   kNodeCapSlack * sphere_report_slack(r_min, D)   what a sphere of any radius in [r_min, D] needs, and
+//   kNodeCapGuard * kF * D                          at least every box's (OBB's) own margin kF * (scale + om),
+// kF = kCullObb with OBBs in the scene, else kCullBox, so that a node without a sphere never sees the cap
+// bind: m = min(fma(factor, om, fscale), cap) is then fma's value bit for bit. kNodeCapSlack (s): a reported
+// point lies within half of the helper's value (its safety factor) of the sphere, and the BVH argument wants
+// it 3/4 of the margin inside the widened box, so s >= 2/3 does; s = 1 leaves a factor 1.5 on the proven
+// bound, 3.7 on the worst hit measured (tests/test_sphere_slack_cpu.py), and measured faster than s = 2
+// (profiles/node_margin_cap_ab.txt).
+// kNodeCapGuard: an OBB's scale is |c|_1 + 1.001 |h|_1 while its world box may sum to |c|_1 + 1.00013 |h|_1,
+// and the two sums round in different orders; 1 % covers both.
+// `reach` (the logging cast, log_margin_om): the part of the operand that pays for the echo replay's
+// reach keeps its full factor, cap + kCullSphere * reach, with om the operand's base part.
+// No cap (+infinity, min keeps fma's value): r_min zero, negative, NaN or infinite (no sphere, or a
+// radius the r-aware form cannot use), or a non-finite s_root, om or reach.
+#ifndef ART_NODE_CAP_SLACK_SCALE
+#define ART_NODE_CAP_SLACK_SCALE 1.0f  // test hook: 0 leaves the cap its floor alone (tests/test_node_margin_gpu.py must fail)
+#endif
+constexpr float kNodeCapSlack = 1.0f * ART_NODE_CAP_SLACK_SCALE, kNodeCapGuard = 1.01f;
+ART_HD float node_abs_sum(float lox, float loy, float loz, float hix, float hiy, float hiz) {
+  return fmaxf(fabsf(lox), fabsf(hix)) + fmaxf(fabsf(loy), fabsf(hiy)) + fmaxf(fabsf(loz), fabsf(hiz));
+}
+// The helper in two steps, so that a kernel pays no division per ray: the r-aware form of sphere_report_slack is a
+// quadratic in D whose coefficients depend on r_min alone (the host keeps them beside DevScene::r_min), and the
+// per-ray step is that polynomial, the square-root form, the floor and the reach term (about 15 VALU).
+ART_HD NodeCapCoef node_cap_coef(float r_min) {
+  NodeCapCoef c;
+  c.a2 = c.a1 = c.a0 = c.on = 0.0f;
+  if (!(r_min > 0.0f) || !ufinite(r_min)) return c;
+  const float k = (ART_SPHERE_SLACK_SCALE * kSlackSafety * kNodeCapSlack) * kSlackEps;
+  c.a2 = k * kSlackDisc / (2.0f * r_min);                    // E / (2 r)'s D^2 part
+  c.a1 = k * kSlackLin;                                      // 16 eps D
+  c.a0 = k * (0.5f * kSlackR2 + kSlackLin) * r_min;          // E / (2 r)'s r part and 16 eps r
+  c.on = 1.0f;
+  return c;
+}
+ART_HD float node_cap_eval(const NodeCapCoef& c, float D, float kf, float reach) {
+  if (!(c.on > 0.0f) || !ufinite(D) || !ufinite(reach)) return INFINITY;
+  const float lin = (c.a2 * D + c.a1) * D + c.a0;
+  return fmaxf(fminf((kNodeCapSlack * kSlackRoot) * D, lin), (kNodeCapGuard * kf) * D) + kCullSphere * reach;
+}
+ART_HD float node_margin_cap(float r_min, float s_root, float om, bool has_obb, float reach) {
+  return node_cap_eval(node_cap_coef(r_min), s_root + om, has_obb ? kCullObb : kCullBox, reach);
+}
+inline void set_r_min(DevScene& sc, float r_min) {
+  sc.r_min = r_min;
+  sc.cap = node_cap_coef(r_min);
+}
+
 // Per-collider decode (shared by the full prep and the resident store's scatter): the hot/cold
 // records at in-kind index i and the broad-phase bounds at global index gi.
 ART_HD void prep_sphere(const art_sphere& s, int i, int gi, SphereRec* __restrict__ osph,

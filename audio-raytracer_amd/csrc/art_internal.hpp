@@ -65,6 +65,9 @@ struct alignas(16) CullRec {
   float hix, hiy, hiz, factor;
 };
 
+// sphere_report_slack's r-aware form at one radius, times the cap's multiple, as a polynomial in the distance
+// bound D: a2 D^2 + a1 D + a0 (node_cap_coef, art_frame_math.hpp); on = 0 (a zero-initialized scene too): no cap.
+struct NodeCapCoef { float a2, a1, a0, on; };
 struct DevScene {
   const SphereRec* sph; const SphereCold* sphc; int ns;
   const AabbRec* aabb; const AabbCold* aabbc; int na;
@@ -102,6 +105,9 @@ struct DevScene {
   // inputs at a bind, lowered by the resident store's syncs (a stale-low value only widens the echo
   // replay's margins, log_margin_om). Like the counts above it travels in the launch's arguments.
   float r_min;
+  // The node margin cap's coefficients for r_min (node_cap_coef, art_frame_math.hpp), set with it (set_r_min):
+  // the kernels evaluate a quadratic in D per ray instead of the helper's division.
+  NodeCapCoef cap;
 };
 // The colliders as the caller gives them (AoS halves) and as the kernels read them (decoded hot and
 // cold records, bounds in global order: spheres, AABBs, OBBs).

@@ -99,9 +99,20 @@ __device__ __forceinline__ bool force_all(const Seg& s, float om) {
 }
 
 // The widened box of a BVH node / collider (margin factor * (scale + om)):
-// entry distance of the segment, or false when it misses the box.
-__device__ __forceinline__ bool node_entry(const Seg& s, const CullRec& r, float om, float& tn) {
-  const float m = __builtin_fmaf(r.factor, om, r.fscale);  // factor * (scale + om), fscale = factor * scale
+// entry distance of the segment, or false when it misses the box. CAP: the margin is at most the ray's
+// `cap` (node_margin_cap, art_frame_math.hpp; +infinity or NaN: no cap). The counting (EX) kernels and the
+// permeation loss rays keep the uncapped margin.
+__device__ __forceinline__ float capped_margin(float m, float cap) { return __builtin_fminf(m, cap); }
+// A ray's cap from the BVH root's stored box (it follows refits and store syncs) and its margin operand.
+__device__ __forceinline__ float ray_margin_cap(const DevScene& sc, float om, bool has_obb) {
+  const CullRec root = ldc(sc.bvh, 0);
+  return node_cap_eval(sc.cap, node_abs_sum(root.lox, root.loy, root.loz, root.hix, root.hiy, root.hiz) + om,
+                       has_obb ? kCullObb : kCullBox, 0.0f);
+}
+template <bool CAP = false>
+__device__ __forceinline__ bool node_entry(const Seg& s, const CullRec& r, float om, float& tn, float cap = 0.0f) {
+  float m = __builtin_fmaf(r.factor, om, r.fscale);  // factor * (scale + om), fscale = factor * scale
+  if (CAP) m = capped_margin(m, cap);
   float tf;
   return slab<false>(s.o.x, s.o.y, s.o.z, s.inv.x, s.inv.y, s.inv.z, r.lox - m, r.loy - m, r.loz - m, r.hix + m, r.hiy + m,
                      r.hiz + m, tn, tf);

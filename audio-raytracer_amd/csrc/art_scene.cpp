@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "art_ctx.hpp"
+#include "art_frame_math.hpp"
 #include "unity_math.hpp"
 
 namespace art {
@@ -151,9 +152,9 @@ int upload_scene(art_ctx* c, Device& dv, const Frame& f, const uint8_t* h_in) {
   DevScene& sc = dv.sc;
   if (f.resident) {  // records and bounds of the last art_colliders_sync
     set_colliders(sc, dv.store.dec, dv.store.n);
-    sc.r_min = c->store.sphere_rmin;
+    set_r_min(sc, c->store.sphere_rmin);
   } else {
-    sc.r_min = spheres_rmin(h_in + f.off_sph, f.ns, INFINITY);
+    set_r_min(sc, spheres_rmin(h_in + f.off_sph, f.ns, INFINITY));
     const RawColliders in = {reinterpret_cast<const art_sphere*>(raw + f.off_sph), reinterpret_cast<const art_aabb*>(raw + f.off_aabb),
                              reinterpret_cast<const art_obb*>(raw + f.off_obb), f.ns, f.na, f.no};
     launch_prep(in, out, dv.stream);

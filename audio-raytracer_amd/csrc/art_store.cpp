@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "art_ctx.hpp"
+#include "art_frame_math.hpp"
 
 using namespace art;
 
@@ -291,7 +292,7 @@ int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt, 
     const int levels_before = dv.sc.bvh_levels;
     const bool rebuild = p.rebuild || dv.sc.bvh_levels == 0 || !dv.sb.bvh;
     set_colliders(dv.sc, v.dec, p.n);
-    dv.sc.r_min = c->store.sphere_rmin;
+    set_r_min(dv.sc, c->store.sphere_rmin);
     // Beside a kd build the lists build on the side stream, as at a bind (they need the decoded
     // records and the targets, not the tree; the sort's surface-area passes occupy a few CUs).
     hipStream_t cells_st = ss;
@@ -335,7 +336,7 @@ int sync_device(art_ctx* c, Device& dv, const SyncPlan& p, bool& cells_rebuilt, 
     return epoch.record(c);
   }
   set_colliders(dv.sc, v.dec, p.n);  // the bound device-resident scene sees the new snapshot
-  dv.sc.r_min = c->store.sphere_rmin;
+  set_r_min(dv.sc, c->store.sphere_rmin);
   if (!p.nd) return epoch.record(c);
   // moved colliders: refit the sorted copies and the BVH in place (device only, no H2D)
   if (fused) {

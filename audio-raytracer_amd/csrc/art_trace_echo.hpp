@@ -104,13 +104,16 @@ __device__ __forceinline__ bool echo_seg_from_hit(const DevScene& sc, const Echo
 // owner = the target). `valid` must be quad-uniform; an invalid segment is reported visible.
 // Work sharing as in the nearest traversal (a blocker of a shared segment ends every traversal of
 // it); nt / nnode accumulate the exact tests and node visits (EX counters).
-template <bool OBB, bool PARK = false>
+// CAP (every kernel but the counting ones): the node margins are capped by the segment's node_margin_cap
+// (art_frame_math.hpp) for its operand |o|_1 + maxd; a thief takes the home segment's cap along.
+template <bool OBB, bool PARK = false, bool CAP = false>
 __device__ __forceinline__ bool quad_echo_core(const DevScene& sc, Seg s, float maxd, int owner, bool valid, int lane,
                                                uint32_t* s_wave, unsigned* nt, unsigned& nnode) {
   const int qd = lane & 3, wq = lane >> 2;
   if (sc.bvh_levels == 0) return true;                         // no colliders: nothing blocks
   float om = fabsf(s.o.x) + fabsf(s.o.y) + fabsf(s.o.z) + maxd;
   bool force = force_all(s, om);
+  float cap = CAP ? ray_margin_cap(sc, om, OBB) : 0.0f;
   unsigned long long fmk = __builtin_amdgcn_ballot_w64(force);  // (the forced lanes as a lane mask, as in the nearest core)
   const int leaf0 = sc.bvh_leaf0, qshift = lane & ~3;
   const BvhRes br = bvh_res(sc);
@@ -149,12 +152,15 @@ __device__ __forceinline__ bool quad_echo_core(const DevScene& sc, Seg s, float 
       // the segment's other derived values too (|o|_1 + maxd, force: the home's own)
       const float dmaxd = __shfl(maxd, src), dom = __shfl(om, src);
       const int dforce = __shfl((int)force, src);
+      float dcap = 0.0f;
+      if (CAP) dcap = __shfl(cap, src);
       if (thief) {
         g = (int)s_wave[(src >> 2) * kBvhStack + dbp];
         sp = bp = 0;
         home = dhome; owner = downer; maxd = dmaxd;
         s = ds;
         om = dom;
+        cap = dcap;
         force = dforce != 0;
       }
       fmk = __builtin_amdgcn_ballot_w64(force);
@@ -174,7 +180,7 @@ __device__ __forceinline__ bool quad_echo_core(const DevScene& sc, Seg s, float 
       ART_DIAG_STEP(nsteps);
       const CullRec r = load_node(br, c0 + qd);
       float tn;
-      const bool h = node_entry(s, r, om, tn);
+      const bool h = node_entry<CAP>(s, r, om, tn, cap);
       // the entered lanes as a mask of scalar ANDs / ORs of single-compare ballots (a ballot of the
       // combined flag would round-trip it through a 0/1 VGPR); empty nodes: art_bvh.hip cull_stored
       const unsigned long long em = fmk | (__builtin_amdgcn_ballot_w64(h) & __builtin_amdgcn_ballot_w64(tn <= maxd));
@@ -227,7 +233,8 @@ constexpr int kDealWords = 16 * 12 + 16 * kLogK;
 // s_rec: the wave's 16 records in LDS.
 // ONE (echo_muffle_kernel): the one-hit fused plan's records at fixed slots (fold_path<true>); the cast
 // stored each hit's echo half already, so a quad stores only a blocked echo's reset 0.
-template <bool OBB, bool HM, bool REPLAY = false, bool ONE = false>
+// EX: the caller is a counting kernel (its traversal keeps the uncapped node margins, quad_echo_core's CAP off).
+template <bool OBB, bool HM, bool REPLAY = false, bool ONE = false, bool EX = false>
 __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs& vp, const uint32_t* count,
                                               unsigned long long* ex, uint32_t blk, int w, uint32_t* s_wave,
                                               const uint32_t* ecnt, int bounce, uint8_t* block, const EchoFromHits& eh,
@@ -386,7 +393,7 @@ __device__ __forceinline__ void vis_quad_body(const DevScene& sc, const VisPairs
       if (lane == 0) atomicAdd(el->count + (blockIdx.x & (kEchoCountSlots - 1)), (unsigned long long)nr | ((unsigned long long)nv << 32));
     }
   }
-  bool visible = quad_echo_core<OBB, HM || ONE>(sc, s, maxd, owner, valid && !replayed, lane, s_wave, nt, nnode);
+  bool visible = quad_echo_core<OBB, HM || ONE, !EX>(sc, s, maxd, owner, valid && !replayed, lane, s_wave, nt, nnode);
   if (REPLAY && replayed) visible = !blocked;
   if (HM) {
     if (valid && qd == 0) reinterpret_cast<uint16_t*>(block)[out_at] = visible ? out_val : (uint16_t)0;  // :76, :142-144
@@ -415,7 +422,7 @@ void vis_kernel(DevScene sc, VisPairs vp, const uint32_t* __restrict__ count, un
                 const uint32_t* __restrict__ ecnt, int bounce, uint8_t* __restrict__ block, EchoFromHits eh) {
   __shared__ uint32_t s_stk[64 * kBvhStack];
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  vis_quad_body<OBB, HM>(sc, vp, count, EX ? ex : nullptr, blockIdx.x, w, s_stk + w * 16 * kBvhStack, ecnt, bounce, block, eh);
+  vis_quad_body<OBB, HM, false, false, EX>(sc, vp, count, EX ? ex : nullptr, blockIdx.x, w, s_stk + w * 16 * kBvhStack, ecnt, bounce, block, eh);
 }
 
 }  // namespace art

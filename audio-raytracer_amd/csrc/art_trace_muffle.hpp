@@ -338,7 +338,7 @@ void echo_muffle_kernel(DevScene sc, FrameParams fp, VisPairs vp, const uint32_t
     uint32_t g;
     int w;
     split(b, groups, g, w);
-    vis_quad_body<OBB, false, !EX && !OBB, true>(sc, vp, count, EX ? ex : nullptr, g, w, s_stk, nullptr, -1, block, eh, &el, s_rec, s_deal);
+    vis_quad_body<OBB, false, !EX && !OBB, true, EX>(sc, vp, count, EX ? ex : nullptr, g, w, s_stk, nullptr, -1, block, eh, &el, s_rec, s_deal);
     return;
   }
   if (groups % 8u == 0u) {

@@ -10,7 +10,8 @@ namespace art {
 
 // Shared-origin node table (TAB kernels): every ray of a workgroup starts at the fan origin O, so a
 // node's widened box relative to O, (lo - m) - O and (hi + m) - O with m = factor * (scale + |O|_1),
-// is the same for all of them. Built once per workgroup in LDS (node_table_build), the node test is
+// capped per ray as node_entry's (CAP: every kernel but the counting ones), is the same for all of
+// them. Built once per workgroup in LDS (node_table_build), the node test is
 // then the slab's multiplies and min / max on the very operands node_entry computes (bit-identical:
 // the same operations in the same order, DESIGN.md §5 item 8 unchanged). Up to kTabNodes nodes
 // (the BVH of <= 4096 colliders: 1365 nodes, 32 KB).
@@ -19,13 +20,16 @@ struct NodeTab {
   float4 a[kTabNodes];  // (lo.x, lo.y, lo.z, hi.x) relative to O, widened
   float2 b[kTabNodes];  // (hi.y, hi.z)
 };
+template <bool CAP, bool OBB>
 __device__ __forceinline__ void node_table_build(const DevScene& sc, vec3 O, NodeTab* tab) {
   const BvhRes br = bvh_res(sc);
   const int nn = sc.bvh_leaf0 + 3 * sc.bvh_leaf0 + 1;
   const float om = fabsf(O.x) + fabsf(O.y) + fabsf(O.z);  // quad_nearest_core's om of every ray at O
+  const float cap = CAP ? ray_margin_cap(sc, om, OBB) : 0.0f;  // (one value per workgroup: nothing per step)
   for (int i = (int)threadIdx.x; i < nn; i += (int)blockDim.x) {
     const CullRec r = load_node(br, i);
-    const float m = __builtin_fmaf(r.factor, om, r.fscale);  // node_entry's margin
+    float m = __builtin_fmaf(r.factor, om, r.fscale);  // node_entry's margin
+    if (CAP) m = capped_margin(m, cap);
     tab->a[i] = make_float4((r.lox - m) - O.x, (r.loy - m) - O.y, (r.loz - m) - O.z, (r.hix + m) - O.x);
     tab->b[i] = make_float2((r.hiy + m) - O.y, (r.hiz + m) - O.z);
   }
@@ -99,6 +103,8 @@ constexpr int kNearestWaves = EX ? 6 : (OBB ? kNearestObbWaves : 8);
 // LOG: every leaf a quad tests is appended to its ray's log (s_log = the wave's 16 records of 16 u16,
 // s_lcnt = their counters; a thief appends to the home ray's), and the node margins use
 // log_margin_om (the echo replay, art_trace_rays.hpp).
+// Every instantiation but the counting ones (EX) caps the node margins by the ray's node_margin_cap
+// (art_frame_math.hpp; TAB: in the table). A thief takes the home ray's cap along with its om.
 template <bool EX, bool OBB, bool PERM = false, bool TAB = false, bool LOG = false>
 __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, bool alive, int lane, uint32_t* my,
                                                   int* s_bound, unsigned long long* s_key, float& best, int& code,
@@ -112,10 +118,14 @@ __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, boo
   if (qd == 0) s_key[wq] = ~0ull;  // the ray's shared result key, opened before the loop
   unsigned nt[3] = {0u, 0u, 0u}, nnode = 0;
   float om = fabsf(s.o.x) + fabsf(s.o.y) + fabsf(s.o.z);
+  constexpr bool CAP = !EX && !TAB;  // (TAB: node_table_build capped the table's boxes)
+  float cap = 0.0f;
   if (LOG) {
     float xcap;
-    om = log_margin_om(sc, s.o, fabsf(s.d.x) + fabsf(s.d.y) + fabsf(s.d.z), xcap);
+    om = log_margin_om(sc, s.o, fabsf(s.d.x) + fabsf(s.d.y) + fabsf(s.d.z), xcap, &cap);
     if (qd == 0) s_lcnt[wq] = 0;
+  } else if (CAP) {
+    cap = ray_margin_cap(sc, om, OBB);
   }
   bool force = force_all(s, om);
   // the forced lanes as a lane mask (wave-uniform, kept in SGPRs): a node test ORs it in with scalar
@@ -173,7 +183,7 @@ __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, boo
     if (TAB) {
       h = node_entry_tab(s, tab, c0 + qd, tn);
     } else {
-      h = node_entry(s, load_node(br, c0 + qd), om, tn);
+      h = node_entry<CAP>(s, load_node(br, c0 + qd), om, tn, cap);
     }
     const float en = fmaxf(tn, 0.0f);
     const bool enter = __builtin_amdgcn_inverse_ballot_w64(fmk) | (h & (en <= lim));  // (empty nodes: art_bvh.hip cull_stored)
@@ -207,6 +217,8 @@ __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, boo
       // the ray's other derived values too (|o|_1, force: the home's own values)
       const float dlim = __shfl(lim, src), dom = __shfl(om, src);
       const int dforce = __shfl((int)force, src);
+      float dcap = 0.0f;
+      if (CAP) dcap = __shfl(cap, src);
       if (thief && mykey != ~0ull && qd == 0) atomicMin(s_key + home, mykey);
       if (thief) {
         g = (int)s_wave[(src >> 2) * kBvhStack + dbp];
@@ -214,6 +226,7 @@ __device__ __forceinline__ void quad_nearest_core(const DevScene& sc, Seg s, boo
         home = dhome;
         s = ds;
         om = dom;
+        cap = dcap;
         force = dforce != 0;
         lim = dlim;
         mykey = ~0ull;  // (the finished ray's result went to its key above)
@@ -337,7 +350,7 @@ __global__ __launch_bounds__(TAB ? 1024 : 256) __attribute__((amdgpu_waves_per_e
   const int rr = 16 * (w & 3) + (lane >> 2);
   uint32_t* my = s_stk + (16 * w + (lane >> 2)) * kBvhStack;
   if constexpr (TAB) {  // the fan origin's node table (every ray of the workgroup starts there)
-    node_table_build(sc, load3(origins, g / nrb), &s_tab);
+    node_table_build<!EX, OBB>(sc, load3(origins, g / nrb), &s_tab);
     __syncthreads();
   }
   unsigned long long* ex = EX ? fp.exec : nullptr;

@@ -33,14 +33,24 @@ struct EchoLog {
 // sphere's own scale covers it). The linear part is sized by the boxes, whose smaller factor (1e-4)
 // has to cover the echo ray's deviation from the primary segment, 1.4e-6 xcap, with the same operand.
 // A non-finite or zero operand gives NaN or infinity there, and the fminf keeps 0.4 xcap.
+// cap (when asked for): the ray's node margin cap (node_margin_cap, art_frame_math.hpp) for this operand. It
+// bounds the base part b alone and the reach term keeps its full factor: cap(S_root + b) + kCullSphere * reach.
+// Where the reach term is the square-root form 0.4 xcap, the replay's step 3 leans on the base part's
+// kCullSphere * r for a sphere's own radius, so the ray takes no cap.
 constexpr float kLogReachSq = 2e-4f, kLogReachLin = 2.8e-2f;
-__device__ __forceinline__ float log_margin_om(const DevScene& sc, vec3 O, float d1, float& xcap) {
+__device__ __forceinline__ float log_margin_om(const DevScene& sc, vec3 O, float d1, float& xcap, float* cap = nullptr) {
   const CullRec root = ldc(sc.bvh, 0);
   xcap = kLogCapFrac * ((root.hix - root.lox) + (root.hiy - root.loy) + (root.hiz - root.loz));
   const float b = 1.05f * (fabsf(O.x) + fabsf(O.y) + fabsf(O.z)) + 4.0f * d1;
   const float r = fminf(sc.r_min, xcap), rx = r + xcap;
   const float reach = ART_SPHERE_SLACK_SCALE * (kLogReachSq * (rx * (rx / r)) + kLogReachLin * xcap);
-  return b + fminf(0.4f * xcap, reach);
+  const float root_reach = 0.4f * xcap, t = fminf(root_reach, reach);
+  if (cap) {
+    NodeCapCoef cc = sc.cap;
+    if (!(reach < root_reach)) cc.on = 0.0f;
+    *cap = node_cap_eval(cc, node_abs_sum(root.lox, root.loy, root.loz, root.hix, root.hiy, root.hiz) + b, kCullBox, t);
+  }
+  return b + t;
 }
 
 constexpr int kLiveCounters = 32;  // per-bounce live-list counters (H <= 32)

@@ -190,6 +190,17 @@ ART_API int art_debug_echo_decided(art_ctx* ctx, uint64_t* replayed, uint64_t* t
  * without spheres). ctx may be NULL when scene_r_min is. */
 ART_API int art_debug_sphere_slack(art_ctx* ctx, float r, float D, float* slack, float* scene_r_min);
 
+/* Diagnostics (tests, ABI 3.11): the per-ray cap of the BVH node margins (the capped
+ * node margin). *cap is the cap of a ray whose margin operand is om in a scene whose smallest sphere
+ * radius is r_min and whose BVH root box has the absolute-coordinate sum s_root (sum over the axes of
+ * max(|lo|, |hi|)); has_obb selects the OBB factor for the cap's floor; reach is the logging cast's reach
+ * term (0 for every other traversal). +infinity means "no cap" (r_min zero, negative or non-finite, or a
+ * non-finite s_root, om or reach). With scene_s_root non-NULL (ctx must then have a bound scene on a
+ * device) it also receives that scene's s_root as the next frame's kernels read it (+infinity for a scene
+ * with a non-finite collider, 0 without colliders); this synchronizes. ctx may be NULL when scene_s_root is. */
+ART_API int art_debug_node_margin_cap(art_ctx* ctx, float r_min, float s_root, float om, int32_t has_obb, float reach,
+                                      float* cap, float* scene_s_root);
+
 /* Context over an explicit list of HIP devices: fans of every art_schedule are sharded
  * contiguously over the list (one HIP stream, one scene copy and one set of buffers per entry).
  * An id may repeat: art_create_on({0, 0, 0}, 3, &ctx) runs the in-process multi-device split and
