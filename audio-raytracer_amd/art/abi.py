@@ -69,6 +69,8 @@ ART_KIND_SPHERE, ART_KIND_AABB, ART_KIND_OBB = 0, 1, 2
 # art_debug_bvh_records (include/art_device.h): which array, and the 32-byte record as it lies in memory
 ART_DEBUG_BVH_BOUNDS, ART_DEBUG_BVH_NODES = 0, 1
 CULL_REC = np.dtype([("lo", "<f4", 3), ("fscale", "<f4"), ("hi", "<f4", 3), ("factor", "<f4")])
+# art_debug_cells_lists (include/art_device.h): which array of the muffle direction-cell lists
+ART_DEBUG_CELLS_STARTS, ART_DEBUG_CELLS_ENTRIES, ART_DEBUG_CELLS_OK, ART_DEBUG_CELLS_FAR, ART_DEBUG_CELLS_INFO = 0, 1, 2, 3, 4
 ART_OUT_HIT_RESULTS = 0x1
 # art_fan.ray_hit_ids: ColliderType (Enums/ColliderType.cs) << 30 | index in that type's array
 ART_COLLIDER_AABB, ART_COLLIDER_OBB, ART_COLLIDER_SPHERE = 1, 2, 3
@@ -250,6 +252,7 @@ SIGNATURES = {
     "art_debug_sphere_slack": (I32, [VP, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "art_debug_node_margin_cap": (I32, [VP, C.c_float, C.c_float, C.c_float, I32, C.c_float, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
+    "art_debug_cells_lists": (I32, [VP, I32, C.POINTER(U32), I32]),
     # art_dsp.h
     "art_dsp_process": (I32, [VP, C.POINTER(art_spatializer_settings), C.POINTER(art_audio_source), I32, I32]),
     "art_dsp_source_params_get": (I32, [C.POINTER(art_spatializer_settings), C.POINTER(art_audio_source), I32,

@@ -288,6 +288,51 @@ class Context:
             assert rc == n
         return buf
 
+    def _cells_words(self, which: int) -> np.ndarray:
+        n = self.lib.art_debug_cells_lists(self.ptr, which, None, 0)
+        if n < 0:
+            self._raise(n)
+        buf = np.zeros(n, dtype=np.uint32)
+        if n:
+            rc = self.lib.art_debug_cells_lists(self.ptr, which, buf.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+            if rc < 0:
+                self._raise(rc)
+            assert rc == n
+        return buf
+
+    def debug_cells_lists(self):
+        """The bound scene's muffle direction-cell lists (art_debug_cells_lists; diagnostics, synchronizes),
+        decoded: (start, code, near_key, near, ok, far, info). start: uint32[T * kCellStride + 1], list l of
+        target t is entries start[t * kCellStride + l] .. start[t * kCellStride + l + 1], l = cell * 3 +
+        collider type. Per arena entry below info["tail"]: code (type << 28 | in-type index; in the 4-byte
+        form the type is that of the list that holds the entry, 0xffffffff for an entry no list holds: the
+        garbage a target's rebuild leaves behind), near_key (the 16-bit sort key) and near (float32 near
+        bounds; None in the 4-byte form, whose bound is the float of near_key << 16). ok: uint32[T], far:
+        float32[T]. info: compact, cap, tail, dropped, kCellG, kCellStride. A scene without lists (cap 0)
+        has empty start, code and far."""
+        info = dict(zip(("compact", "cap", "tail", "dropped", "kCellG", "kCellStride"),
+                        (int(v) for v in self._cells_words(abi.ART_DEBUG_CELLS_INFO))))
+        start = self._cells_words(abi.ART_DEBUG_CELLS_STARTS)
+        words = self._cells_words(abi.ART_DEBUG_CELLS_ENTRIES)
+        ok = self._cells_words(abi.ART_DEBUG_CELLS_OK)
+        far = self._cells_words(abi.ART_DEBUG_CELLS_FAR).view(np.float32)
+        if info["compact"]:
+            stride, lists = info["kCellStride"], 6 * info["kCellG"] ** 2 * 3
+            code = np.full(words.size, 0xffffffff, np.uint32)
+            for t in range(ok.size if start.size else 0):
+                s = start[t * stride:t * stride + lists + 1].astype(np.int64)
+                ln = np.diff(s)
+                if ln.sum() == 0 or (ln < 0).any() or s[-1] > words.size:  # (malformed starts: left untyped)
+                    continue
+                ty = np.repeat(np.arange(lists, dtype=np.uint32) % 3, ln)
+                b = int(s[0])
+                code[b:b + ty.size] = (ty << np.uint32(28)) | (words[b:b + ty.size] & np.uint32(0xffff))
+            return start, code, words >> np.uint32(16), None, ok, far, info
+        pair = words.reshape(-1, 2)
+        near_bits = pair[:, 1].copy()
+        near_key = np.where(near_bits.view(np.int32) <= 0, np.uint32(0), near_bits >> np.uint32(16))
+        return start, pair[:, 0].copy(), near_key, near_bits.view(np.float32), ok, far, info
+
     def debug_last_plan(self) -> int:
         """ART_PLAN_* bits of the launch plan the throughput raytrace stage took for the last frame
         (art_debug_last_plan; diagnostics). 0 after a reference-order or counting frame."""

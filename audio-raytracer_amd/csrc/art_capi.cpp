@@ -52,8 +52,8 @@ namespace {
 // added and removed on a bound scene (art_targets_reserve, art_target_capacity, art_targets_last_resize,
 // art_debug_target_sync_map); 3.8: art_debug_sphere_slack; 3.9: art_debug_bvh_records;
 // 3.10: colliders added and removed on a bound scene (art_colliders_reserve, art_collider_capacity,
-// art_colliders_last_resize); 3.11: art_debug_node_margin_cap
-constexpr uint32_t kAbiVersion = (3u << 16) | 11u;
+// art_colliders_last_resize); 3.11: art_debug_node_margin_cap; 3.12: art_debug_cells_lists
+constexpr uint32_t kAbiVersion = (3u << 16) | 12u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {
@@ -765,6 +765,38 @@ ART_API int art_debug_cells_arena(art_ctx* c, uint64_t* used, uint64_t* cap, uin
   *cap = dv.cb.cap;
   *dropped_targets = v[1];
   return ART_OK;
+}
+
+ART_API int art_debug_cells_lists(art_ctx* c, int32_t which, uint32_t* out, int32_t cap) {
+  if (!c || (!out && cap > 0) || cap < 0 || which < ART_DEBUG_CELLS_STARTS || which > ART_DEBUG_CELLS_INFO) return ART_E_INVALID;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
+  if (c->devs.empty() || !c->devs[0].bound) return fail(c, ART_E_STATE, "no scene bound (art_scene_bind)");
+  Device& dv = c->devs[0];
+  const CellBufs& cb = dv.cb;
+  const size_t T = (size_t)std::max(dv.sc.T, 0);
+  HIP_TRY(c, hipSetDevice(dv.id));
+  HIP_TRY(c, hipDeviceSynchronize());
+  uint32_t tail[2] = {0u, 0u};
+  if (cb.tail) HIP_TRY(c, hipMemcpy(tail, cb.tail, sizeof tail, hipMemcpyDeviceToHost));
+  const uint32_t info[6] = {cb.compact, cb.cap, tail[0], tail[1], (uint32_t)kCellG, (uint32_t)kCellStride};
+  const void* src = nullptr;
+  size_t count = 0;  // 4-byte words
+  switch (which) {
+    case ART_DEBUG_CELLS_STARTS: src = cb.start; count = cb.cap ? T * kCellStride + 1 : 0; break;
+    case ART_DEBUG_CELLS_ENTRIES: src = cb.ent_s; count = (size_t)std::min(tail[0], cb.cap) * (cb.compact ? 1 : 2); break;
+    case ART_DEBUG_CELLS_OK: src = cb.ok; count = T; break;
+    case ART_DEBUG_CELLS_FAR: src = cb.far; count = cb.cap ? T : 0; break;  // (not written without lists)
+    default: break;
+  }
+  if (which == ART_DEBUG_CELLS_INFO) {
+    count = 6;
+    if (cap > 0) memcpy(out, info, std::min<size_t>(count, (size_t)cap) * sizeof(uint32_t));
+    return (int)count;
+  }
+  if (count > (size_t)INT32_MAX) return fail(c, ART_E_UNSUPPORTED, "%s: more than 2^31 - 1 words", __func__);
+  const size_t m = std::min(count, (size_t)cap);
+  if (m > 0 && src) HIP_TRY(c, hipMemcpy(out, src, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return (int)count;
 }
 
 ART_API int art_kernel_timing(art_ctx* c, art_kernel_times* out) {

@@ -201,6 +201,26 @@ ART_API int art_debug_sphere_slack(art_ctx* ctx, float r, float D, float* slack,
 ART_API int art_debug_node_margin_cap(art_ctx* ctx, float r_min, float s_root, float om, int32_t has_obb, float reach,
                                       float* cap, float* scene_s_root);
 
+/* Diagnostics (tests, ABI 3.12): the muffle direction-cell lists of the bound scene on the context's first
+ * device, as they lie in device memory, in 4-byte words. Copies at most cap words to out (out may be NULL
+ * when cap is 0) and returns the array's word count, whatever cap is, or a negative art error (ART_E_STATE:
+ * no scene bound; ART_E_UNSUPPORTED: the CPU backend). T is the scene's current target count.
+ * ART_DEBUG_CELLS_STARTS: uint32[T * kCellStride + 1], the list starts: per target kCells * 3 lists (cell
+ * (face * kCellG + j) * kCellG + i, then the collider type: sphere, AABB, OBB) followed by pad starts that
+ * equal the target's end; list l of target t is ent[start[t * kCellStride + l] .. start[t * kCellStride + l + 1]).
+ * ART_DEBUG_CELLS_ENTRIES: the sorted arena [0, tail): one word per entry (in-type index | near key << 16)
+ * when INFO's compact is 1, else two words per entry (type << 28 | in-type index, bits of the near bound).
+ * ART_DEBUG_CELLS_OK: uint32[T], 1 for a target that has lists. ART_DEBUG_CELLS_FAR: float[T] as bits, the
+ * segment length each target's lists were built for. ART_DEBUG_CELLS_INFO: {compact, cap (entries), tail
+ * (entries in use), targets dropped for capacity, kCellG, kCellStride}. A scene without lists (cap 0)
+ * returns 0 for STARTS, ENTRIES and FAR. Synchronizes. */
+#define ART_DEBUG_CELLS_STARTS  0
+#define ART_DEBUG_CELLS_ENTRIES 1
+#define ART_DEBUG_CELLS_OK      2
+#define ART_DEBUG_CELLS_FAR     3
+#define ART_DEBUG_CELLS_INFO    4
+ART_API int art_debug_cells_lists(art_ctx* ctx, int32_t which, uint32_t* out, int32_t cap);
+
 /* Context over an explicit list of HIP devices: fans of every art_schedule are sharded
  * contiguously over the list (one HIP stream, one scene copy and one set of buffers per entry).
  * An id may repeat: art_create_on({0, 0, 0}, 3, &ctx) runs the in-process multi-device split and

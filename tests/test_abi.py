@@ -27,7 +27,7 @@ def test_headers_declare_expected_surface():
     names = declared_symbols()
     for n in ("art_create", "art_schedule", "art_is_completed", "art_complete", "art_destroy", "art_last_error",
               "art_scene_bind", "art_launch_device", "art_synth_scene", "art_debug_leaf_order", "art_debug_last_plan",
-              "art_debug_bvh_records"):
+              "art_debug_bvh_records", "art_debug_cells_lists"):
         assert n in names
 
 
@@ -79,8 +79,24 @@ def test_header_struct_sizes_match_bindings(tmp_path):
 def test_version():
     v = art.load_library().art_version()
     # 3.0: art_kernel_times per kernel family (a grown struct: major bump); 3.1: ART_CTX_EVENT_EACH_LAUNCH,
-    # art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*; 3.9: art_debug_bvh_records
-    assert v >> 16 == 3 and (v & 0xffff) >= 9
+    # art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*; 3.9: art_debug_bvh_records;
+    # 3.12: art_debug_cells_lists
+    assert v >> 16 == 3 and (v & 0xffff) >= 12
+
+
+def test_cells_lists_hook_without_device():
+    """art_debug_cells_lists (ABI 3.12): the binding's ART_DEBUG_CELLS_* values are the header's, and the CPU
+    backend (no device lists) refuses the query."""
+    hdr = open(os.path.join(ROOT, "include", "art_device.h")).read()
+    in_hdr = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define (ART_DEBUG_CELLS_\w+)\s+(\d+)\b", hdr)}
+    assert sorted(in_hdr.values()) == [0, 1, 2, 3, 4]
+    for name, v in in_hdr.items():
+        assert getattr(abi, name) == v
+    with art.Context(0) as cpu:
+        buf = (C.c_uint32 * 8)()
+        assert cpu.lib.art_debug_cells_lists(cpu.ptr, abi.ART_DEBUG_CELLS_INFO, buf, 8) == abi.ART_E_UNSUPPORTED
+        assert cpu.lib.art_debug_cells_lists(cpu.ptr, 5, buf, 8) == abi.ART_E_INVALID
+        assert cpu.lib.art_debug_cells_lists(cpu.ptr, abi.ART_DEBUG_CELLS_INFO, None, 8) == abi.ART_E_INVALID
 
 
 def test_plan_bits_match_header():
