@@ -53,6 +53,7 @@ ART_CTX_RESIDENT_COLLIDERS = 0x20  # art_colliders.h
 ART_CTX_TIME_EACH_KERNEL = 0x200
 ART_CTX_EVENT_EACH_LAUNCH = 0x400  # art_launch_device records its completion event (the caller may drop its stream)
 ART_CTX_RESIDENT_TARGETS = 0x800  # art_colliders.h: positions and T come from the last art_targets_sync
+ART_CTX_TARGET_OWNERS_FOLLOW = 0x1000  # art_colliders.h: a swapped target's colliders take its new index
 # art_debug_last_plan: the launch plan of the throughput raytrace stage (art_device.h)
 ART_PLAN_FUSED, ART_PLAN_HM, ART_PLAN_SPLIT, ART_PLAN_FOLD, ART_PLAN_PER_BOUNCE = 0x1, 0x2, 0x4, 0x8, 0x10
 ART_PLAN_TAB, ART_PLAN_OBB, ART_PLAN_EX, ART_PLAN_CHUNKED = 0x20, 0x40, 0x80, 0x100
@@ -267,6 +268,8 @@ SIGNATURES = {
     "art_dsp_mix_device": (I32, [VP, VP, VP, VP, I32, I32, I32, VP, VP]),
     "art_dsp_tick_mix_device": (I32, [VP, VP, U32, I32, VP, VP, VP, VP, I32, VP, VP, VP]),
     "art_dsp_mix_host": (I32, [VP, VP, VP, I32, I32, I32, VP]),
+    "art_dsp_sources_follow_host": (I32, [VP, I32, I32, VP, I32, I32, VP, VP, VP, VP, C.c_float]),
+    "art_dsp_sources_follow_device": (I32, [VP, VP, I32, I32, VP, I32, I32, VP, VP, VP, VP, C.c_float, VP]),
     # art_colliders.h
     "art_collider_add": (I32, [VP, I32, VP, C.POINTER(I32)]),
     "art_collider_set": (I32, [VP, I32, I32, VP]),
@@ -295,6 +298,9 @@ SIGNATURES = {
     "art_target_capacity": (I32, [VP]),
     "art_targets_last_resize": (I32, [VP, C.POINTER(art_target_resize_stats)]),
     "art_debug_target_sync_map": (I32, [VP, VP, I32]),
+    "art_target_follow_map": (I32, [VP, VP, I32, C.POINTER(I32)]),
+    "art_target_follow_mark": (I32, [VP]),
+    "art_target_last_remove_owners": (I32, [VP, VP]),
     "art_device_count": (I32, []),
     "art_create_on": (I32, [C.POINTER(I32), I32, C.POINTER(VP)]),
     # art_synth.h

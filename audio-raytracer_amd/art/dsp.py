@@ -13,6 +13,9 @@ scalars, on the device and on the caller's stream, or on the host.
 The listener mix (mix_device, tick_mix_device, mix_host) is the server form of the chain: one dry
 buffer per audio target in, shared by every fan, and one mix per fan out, the fan's T sources summed
 in ascending target order (include/art_dsp.h has the contract).
+
+sources_follow_device / sources_follow_host move the per-source filter states and volumes to the new
+numbering s = f * T + t after targets were added or removed (TargetStore.follow_map, art/targets.py).
 """
 from __future__ import annotations
 
@@ -219,6 +222,51 @@ def tick_mix_device(ctx, d_block, fan_count: int, d_listeners, d_dry, d_state, f
     mix over d_dry (float [T][frames][2]) into d_mix (float [fan_count][frames][2])."""
     rc = ctx.lib.art_dsp_tick_mix_device(ctx.ptr, _dptr(d_block), out_flags, fan_count, _dptr(d_listeners), _dptr(d_volume),
                                          _dptr(d_dry), _dptr(d_state), frames, _dptr(d_params), _dptr(d_mix), stream)
+    if rc:
+        ctx._raise(rc)
+
+
+def sources_follow_host(target_src, target_count_old: int, fan_count_new: int, fan_count_old: int, state_old: np.ndarray,
+                        volume_old: np.ndarray | None = None, fan_src=None, new_volume: float = 1.0,
+                        want_volume: bool = True):
+    """art_dsp_sources_follow_host: the states (abi.DSP_STATE [fan_count_old * T_old]) and volumes moved
+    to the numbering s = f * T_new + t by target_src (int32 [T_new]) and fan_src (int32 [fan_count_new]
+    or None = identity). Returns (state_new, volume_new); volume_new is None when want_volume is False."""
+    ts = np.ascontiguousarray(target_src, np.int32).reshape(-1)
+    T_new = ts.size
+    fs = None if fan_src is None else np.ascontiguousarray(fan_src, np.int32).reshape(-1)
+    assert fs is None or fs.size == fan_count_new
+    n_old = fan_count_old * target_count_old
+    assert state_old.dtype == abi.DSP_STATE and state_old.size == n_old and state_old.flags["C_CONTIGUOUS"]
+    vo = None
+    if volume_old is not None:
+        vo = np.ascontiguousarray(volume_old, np.float32).reshape(-1)
+        assert vo.size == n_old
+    state_new = np.zeros(fan_count_new * T_new, abi.DSP_STATE)
+    volume_new = np.zeros(fan_count_new * T_new, np.float32) if want_volume else None
+    rc = abi.load_library().art_dsp_sources_follow_host(
+        ts.ctypes.data, T_new, target_count_old, None if fs is None else fs.ctypes.data, fan_count_new, fan_count_old,
+        state_old.ctypes.data, None if vo is None else vo.ctypes.data, state_new.ctypes.data,
+        None if volume_new is None else volume_new.ctypes.data, new_volume)
+    if rc:
+        raise ValueError(f"art_dsp_sources_follow_host: {abi.ERROR_NAMES.get(rc, rc)}")
+    return state_new, volume_new
+
+
+def sources_follow_device(ctx, target_src, target_count_new: int, target_count_old: int, fan_count_new: int,
+                          fan_count_old: int, d_state_old, d_state_new, d_volume_old=None, d_volume_new=None,
+                          d_fan_src=None, new_volume: float = 1.0, stream: int | None = None):
+    """art_dsp_sources_follow_device on `stream` (not synchronised), out of place. target_src is a host
+    int32 array, or None = the store's follow map (the counts must then be the store's synced count and
+    the map's base count); the other buffers are torch tensors or raw device pointers."""
+    ts = None
+    if target_src is not None:
+        ts = np.ascontiguousarray(target_src, np.int32).reshape(-1)
+        assert ts.size == target_count_new
+    rc = ctx.lib.art_dsp_sources_follow_device(ctx.ptr, None if ts is None else ts.ctypes.data, target_count_new,
+                                               target_count_old, _dptr(d_fan_src), fan_count_new, fan_count_old,
+                                               _dptr(d_state_old), _dptr(d_volume_old), _dptr(d_state_new),
+                                               _dptr(d_volume_new), new_volume, stream)
     if rc:
         ctx._raise(rc)
 

@@ -5,7 +5,9 @@ NativeJobBatch<float3> AudioTargetPositions. `add` / `set` / `remove_swapback` e
 mirror; `sync` is UpdateJobBatch and publishes the mirror. On a bound device scene a sync that only
 moves targets uploads the moved positions and rebuilds those targets' muffle cell lists alone.
 Frames then take the positions and the target count from the store (`resident_targets_frame`,
-ART_CTX_RESIDENT_TARGETS).
+ART_CTX_RESIDENT_TARGETS). `follow_map` / `follow_mark` give the syncs' maps composed since the last
+mark, for arrays kept per target or per source (art.dsp.sources_follow_device); with
+ART_CTX_TARGET_OWNERS_FOLLOW a `remove_swapback` also re-numbers the swapped target's colliders.
 """
 from __future__ import annotations
 
@@ -101,6 +103,26 @@ class TargetStore:
         src = np.full(max(n, 1), -2, np.int32)
         assert self._check(self.ctx.lib.art_debug_target_sync_map(self.ctx.ptr, src.ctypes.data, n)) == n
         return src[:n]
+
+    def follow_map(self) -> tuple[np.ndarray, int]:
+        """art_target_follow_map: (src, base_count). src[i] is the index the target now at synced index
+        i held in the base list (the synced list at the last follow_mark), -1 if it was not in it."""
+        n = self.synced_count()
+        src = np.full(max(n, 1), -2, np.int32)
+        base = C.c_int32()
+        assert self._check(self.ctx.lib.art_target_follow_map(self.ctx.ptr, src.ctypes.data, n, C.byref(base))) == n
+        return src[:n], base.value
+
+    def follow_mark(self):
+        """art_target_follow_mark: the synced list becomes the base list of the follow map."""
+        self._check(self.ctx.lib.art_target_follow_mark(self.ctx.ptr))
+
+    def last_remove_owners(self) -> list[int]:
+        """Collider records re-numbered by the most recent remove_swapback (ART_CTX_TARGET_OWNERS_FOLLOW),
+        per kind: spheres, AABBs, OBBs."""
+        out = np.zeros(3, np.int32)
+        self._check(self.ctx.lib.art_target_last_remove_owners(self.ctx.ptr, out.ctypes.data))
+        return out.tolist()
 
     def cells_arena(self) -> dict:
         """art_debug_cells_arena of the bound scene (diagnostics, synchronizes)."""

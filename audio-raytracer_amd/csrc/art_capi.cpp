@@ -52,8 +52,11 @@ namespace {
 // added and removed on a bound scene (art_targets_reserve, art_target_capacity, art_targets_last_resize,
 // art_debug_target_sync_map); 3.8: art_debug_sphere_slack; 3.9: art_debug_bvh_records;
 // 3.10: colliders added and removed on a bound scene (art_colliders_reserve, art_collider_capacity,
-// art_colliders_last_resize); 3.11: art_debug_node_margin_cap; 3.12: art_debug_cells_lists
-constexpr uint32_t kAbiVersion = (3u << 16) | 12u;
+// art_colliders_last_resize); 3.11: art_debug_node_margin_cap; 3.12: art_debug_cells_lists;
+// 3.13: per-source data and collider owners follow the targets (art_target_follow_map, art_target_follow_mark,
+// art_dsp_sources_follow_host, art_dsp_sources_follow_device, ART_CTX_TARGET_OWNERS_FOLLOW,
+// art_target_last_remove_owners)
+constexpr uint32_t kAbiVersion = (3u << 16) | 13u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {

@@ -244,6 +244,12 @@ struct TargetStore {
   // then, -1 for a target added since (add appends -1, a swap-back carries the last one's along)
   std::vector<int> src;           // count
   std::vector<int> last_map;      // synced: src at the last sync (art_debug_target_sync_map)
+  // the syncs' maps composed since the last art_target_follow_mark: follow[i] is the index the target
+  // now at synced index i held in the base list (the synced list at the mark; empty before the first
+  // sync), -1 if it was not in it (art_target_follow_map)
+  std::vector<int> follow;        // synced
+  int base_count = 0;
+  int last_remove_owners[3] = {0, 0, 0};  // art_target_last_remove_owners
   int reserved = 0;               // art_targets_reserve
   art_target_resize_stats last_resize{};
 };

@@ -525,6 +525,73 @@ void launch_dsp_tick_params(const DspTickArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(dsp_tick_params_kernel, dim3((a.count + kDspBlock - 1) / kDspBlock), dim3(kDspBlock), 0, st, a);
 }
 
+// Sources follow the targets: the contract of art_dsp_sources_follow_host, literally.
+void dsp_sources_follow_host(const int32_t* target_src, int T_new, int T_old, const int32_t* fan_src, int F_new, int F_old,
+                             const art_dsp_state* state_old, const float* volume_old, art_dsp_state* state_new,
+                             float* volume_new, float new_volume) {
+  for (int f = 0; f < F_new; ++f) {
+    const int fo = fan_src ? fan_src[f] : f;
+    for (int t = 0; t < T_new; ++t) {
+      const size_t s = (size_t)f * T_new + t;
+      const int to = target_src[t];
+      if (fo >= 0 && fo < F_old && to >= 0 && to < T_old) {
+        const size_t so = (size_t)fo * T_old + to;
+        std::memcpy(&state_new[s], &state_old[so], sizeof(art_dsp_state));
+        if (volume_new) volume_new[s] = volume_old ? volume_old[so] : new_volume;
+      } else {
+        std::memset(&state_new[s], 0, sizeof(art_dsp_state));
+        if (volume_new) volume_new[s] = new_volume;
+      }
+    }
+  }
+}
+
+namespace {
+
+constexpr int kFollowBlock = 256;
+
+// Two lanes per source s = f * T_new + t, each moves one 16-B half of the 32-B state (the lanes of a
+// wave read and write adjacent halves: full lines for an identity map, 32-B pieces for any other);
+// the even lane writes the volume. A pure gather: the old arrays are only read, and only at a source
+// whose fan and target index lie inside them. Arrays are assumed aligned to 4 bytes only: 16-B
+// accesses when both state arrays allow them (a.wide), four 4-B ones otherwise. The target map is
+// read from the argument block.
+__global__ __launch_bounds__(kFollowBlock) void dsp_sources_follow_kernel(DspFollowArgs a) {
+  const uint32_t i = blockIdx.x * (uint32_t)kFollowBlock + threadIdx.x;  // < 2^32: count <= 2^31 - 1
+  const uint32_t s = i >> 1, h = i & 1u;
+  if (s >= a.count) return;
+  const uint32_t f = s / (uint32_t)a.T_new, t = s - f * (uint32_t)a.T_new;
+  const int fo = a.fan_src ? a.fan_src[f] : (int)f;
+  const int to = a.target_src[t];
+  const bool old = fo >= 0 && fo < a.F_old && to >= 0 && to < a.T_old;
+  const size_t so = old ? (size_t)fo * (size_t)a.T_old + (size_t)to : 0;
+  const uint8_t* src = a.state_old + so * sizeof(art_dsp_state) + h * 16u;
+  uint8_t* dst = a.state_new + (size_t)s * sizeof(art_dsp_state) + h * 16u;
+  if (a.wide) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (old) v = *reinterpret_cast<const uint4*>(src);
+    *reinterpret_cast<uint4*>(dst) = v;
+  } else {
+    uint32_t v[4] = {0u, 0u, 0u, 0u};
+    if (old) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = reinterpret_cast<const uint32_t*>(src)[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) reinterpret_cast<uint32_t*>(dst)[k] = v[k];
+  }
+  if (h == 0u && a.volume_new) a.volume_new[s] = (old && a.volume_old) ? a.volume_old[so] : a.new_volume;
+}
+
+}  // namespace
+
+void launch_dsp_sources_follow(const DspFollowArgs& a, hipStream_t st) {
+  if (a.count == 0u) return;
+  const unsigned long long lanes = 2ull * a.count;
+  hipLaunchKernelGGL(dsp_sources_follow_kernel, dim3((unsigned)((lanes + kFollowBlock - 1) / kFollowBlock)),
+                     dim3(kFollowBlock), 0, st, a);
+}
+
 void launch_dsp(float* data, unsigned long long data_bytes, const long long* offsets, const int* frames_of,
                 int frames_all, const art_dsp_source_params* params, art_dsp_state* state, int count, hipStream_t st) {
   if (count <= 0) return;

@@ -277,4 +277,81 @@ ART_API int art_dsp_mix_host(const art_dsp_source_params* params, art_dsp_state*
   return ART_OK;
 }
 
+// ---------------------------------------------------------------------------- sources follow the targets
+// Every entry of a target map lies in [-1, T_old).
+static bool follow_map_ok(const int32_t* target_src, int32_t T_new, int32_t T_old) {
+  for (int32_t t = 0; t < T_new; ++t)
+    if (target_src[t] < -1 || target_src[t] >= T_old) return false;
+  return true;
+}
+
+ART_API int art_dsp_sources_follow_host(const int32_t* target_src, int32_t target_count_new, int32_t target_count_old,
+                                        const int32_t* fan_src, int32_t fan_count_new, int32_t fan_count_old,
+                                        const art_dsp_state* state_old, const float* volume_old,
+                                        art_dsp_state* state_new, float* volume_new, float new_volume) {
+  if (target_count_new < 0 || target_count_old < 0 || fan_count_new < 0 || fan_count_old < 0) return ART_E_INVALID;
+  if (fan_count_new == 0 || target_count_new == 0) return ART_OK;  // no source to write
+  if (!target_src || !state_new) return ART_E_INVALID;
+  if (fan_count_old > 0 && target_count_old > 0 && !state_old) return ART_E_INVALID;
+  if (!follow_map_ok(target_src, target_count_new, target_count_old)) return ART_E_INVALID;
+  dsp_sources_follow_host(target_src, target_count_new, target_count_old, fan_src, fan_count_new, fan_count_old, state_old,
+                          volume_old, state_new, volume_new, new_volume);
+  return ART_OK;
+}
+
+ART_API int art_dsp_sources_follow_device(art_ctx* c, const int32_t* target_src, int32_t target_count_new,
+                                          int32_t target_count_old, const int32_t* d_fan_src, int32_t fan_count_new,
+                                          int32_t fan_count_old, const art_dsp_state* d_state_old, const float* d_volume_old,
+                                          art_dsp_state* d_state_new, float* d_volume_new, float new_volume, void* stream) {
+  if (!c) return ART_E_INVALID;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
+  if (target_count_new < 0 || target_count_old < 0 || fan_count_new < 0 || fan_count_old < 0)
+    return fail(c, ART_E_INVALID, "%s: negative count", __func__);
+  if (!target_src) {  // the store's follow map: the caller's counts must be the store's
+    const TargetStore& t = c->targets;
+    if (target_count_new != t.synced || target_count_old != t.base_count)
+      return fail(c, ART_E_INVALID, "%s: target counts %d <- %d are not the store's (synced %d, follow base %d)", __func__,
+                  target_count_new, target_count_old, t.synced, t.base_count);
+    target_src = t.follow.data();
+  }
+  if (target_count_new > kMaxTargets || target_count_old > kMaxTargets)
+    return fail(c, ART_E_UNSUPPORTED, "%s: more than %d targets", __func__, kMaxTargets);
+  const long long count = (long long)fan_count_new * target_count_new, count_old = (long long)fan_count_old * target_count_old;
+  if (count > 0x7fffffffLL) return fail(c, ART_E_UNSUPPORTED, "%s: more than 2^31 - 1 sources", __func__);
+  if (count == 0) return ART_OK;
+  if (!d_state_new || (count_old > 0 && !d_state_old)) return fail(c, ART_E_INVALID, "%s: bad device buffers", __func__);
+  if (!follow_map_ok(target_src, target_count_new, target_count_old))
+    return fail(c, ART_E_INVALID, "%s: a target_src entry lies outside [-1, %d)", __func__, target_count_old);
+  const uintptr_t so = reinterpret_cast<uintptr_t>(d_state_old), vo = reinterpret_cast<uintptr_t>(d_volume_old),
+                  sn = reinterpret_cast<uintptr_t>(d_state_new), vn = reinterpret_cast<uintptr_t>(d_volume_new),
+                  fs = reinterpret_cast<uintptr_t>(d_fan_src);
+  if ((so | vo | sn | vn | fs) & 3) return fail(c, ART_E_INVALID, "%s: device arrays must be 4-byte aligned", __func__);
+  {  // out of place only: no old array may overlap a new one
+    struct Range { uintptr_t p; unsigned long long bytes; };
+    const Range olds[2] = {{so, (unsigned long long)count_old * sizeof(art_dsp_state)}, {vo, (unsigned long long)count_old * 4ull}};
+    const Range news[2] = {{sn, (unsigned long long)count * sizeof(art_dsp_state)}, {vn, (unsigned long long)count * 4ull}};
+    for (const Range& o : olds)
+      for (const Range& n : news)
+        if (o.p && n.p && o.bytes && o.p < n.p + n.bytes && n.p < o.p + o.bytes)
+          return fail(c, ART_E_INVALID, "%s: an old and a new array overlap (the call is out of place only)", __func__);
+  }
+  if (c->devs.empty()) return fail(c, ART_E_STATE, "%s: the context has no device", __func__);
+  DspFollowArgs a{};
+  a.state_old = reinterpret_cast<const uint8_t*>(d_state_old);
+  a.volume_old = d_volume_old;
+  a.state_new = reinterpret_cast<uint8_t*>(d_state_new);
+  a.volume_new = d_volume_new;
+  a.fan_src = d_fan_src;
+  a.T_new = target_count_new; a.T_old = target_count_old; a.F_old = fan_count_old;
+  a.count = (uint32_t)count;
+  a.new_volume = new_volume;
+  a.wide = ((so | sn) & 15) == 0 ? 1 : 0;
+  for (int32_t t = 0; t < target_count_new; ++t) a.target_src[t] = (int16_t)target_src[t];
+  Device& dv = c->devs[0];
+  HIP_TRY(c, hipSetDevice(dv.id));
+  launch_dsp_sources_follow(a, static_cast<hipStream_t>(stream));
+  HIP_TRY(c, hipGetLastError());
+  return ART_OK;
+}
+
 }  // extern "C"

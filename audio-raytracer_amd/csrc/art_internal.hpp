@@ -185,6 +185,22 @@ void dsp_mix_host(const art_dsp_source_params* params, art_dsp_state* state, con
                   int frames, float* mix);
 void launch_dsp_mix(const float* dry, const art_dsp_source_params* params, art_dsp_state* state, int fan_count, int T,
                     int frames, float* mix, hipStream_t st);
+// Sources follow the targets (art_dsp_sources_follow_*): state_new / volume_new [count = F_new * T_new]
+// gathered from the old arrays by target_src (in the argument block: T <= kMaxTargets) and fan_src.
+struct DspFollowArgs {
+  const uint8_t* state_old; const float* volume_old;  // [F_old * T_old], only read; volume_old may be nullptr
+  uint8_t* state_new; float* volume_new;              // [count]; volume_new may be nullptr
+  const int32_t* fan_src;                             // device [F_new] or nullptr = identity
+  int T_new, T_old, F_old;
+  uint32_t count;                                     // F_new * T_new <= 2^31 - 1
+  float new_volume;
+  int wide;                                           // both state arrays are 16-B aligned
+  int16_t target_src[kMaxTargets];                    // [T_new], each in [-1, T_old)
+};
+void dsp_sources_follow_host(const int32_t* target_src, int T_new, int T_old, const int32_t* fan_src, int F_new, int F_old,
+                             const art_dsp_state* state_old, const float* volume_old, art_dsp_state* state_new,
+                             float* volume_new, float new_volume);
+void launch_dsp_sources_follow(const DspFollowArgs& a, hipStream_t st);
 
 // Dirty records of a resident-store sync (art_colliders_sync): the update image (indices and
 // records per kind) and the resident lists and decoded records they are scattered into.

@@ -407,7 +407,10 @@ void commit_sync(art_ctx* c, const SyncPlan& p, bool cells_rebuilt, art_collider
   rs.bytes_uploaded = s.last_sync.bytes_uploaded;
   s.relabel_pending = rs.kept_bound && !rs.bvh_rebuilt;
   s.last_resize = rs;
-  if (rs.kept_bound) {  // counting frames: the colliders not owned, summed over the targets (count_nonowned)
+  // counting frames: the colliders not owned, summed over the targets (count_nonowned). Also after a
+  // sync that changed no count: it may have changed owners (art_collider_set, or a target remove with
+  // ART_CTX_TARGET_OWNERS_FOLLOW), after a target sync that counted with the records of before.
+  if (c->fr.resident && is_bound) {
     c->nonowned.assign(3, 0);
     for (int k = 0; k < 3; ++k) {
       uint64_t owned = 0;
@@ -641,6 +644,14 @@ void commit_target_sync(art_ctx* c, const TargetSyncPlan& p, int rebuilt, bool f
     for (Device& dv : c->devs) dv.bound = false;  // T is in the frame layout: bind again
   }
   t.last_map = p.map;
+  {  // the follow map: this sync's map composed onto the ones since the last mark
+    std::vector<int> nf((size_t)p.n);
+    for (int i = 0; i < p.n; ++i) {
+      const int s = p.map[(size_t)i];
+      nf[(size_t)i] = (s >= 0 && (size_t)s < t.follow.size()) ? t.follow[(size_t)s] : -1;
+    }
+    t.follow.swap(nf);
+  }
   for (int i = 0; i < p.n; ++i) t.src[(size_t)i] = i;
   // a full rebuild used the colliders' synced records: they are the lists' base now
   if (full_rebuild && c->fr.resident) snapshot_cell_base(c);
@@ -701,12 +712,28 @@ ART_API int art_target_set_many(art_ctx* c, const int32_t* ids, const float* pos
 ART_API int art_target_remove_swapback(art_ctx* c, int32_t id) {
   if (!c) return ART_E_INVALID;
   TargetStore& t = c->targets;
+  for (int& n : t.last_remove_owners) n = 0;
   if (id < 0 || id >= t.count) return ART_OK;  // skipped, as art_collider_remove_swapback
   const int last = t.count - 1;
   if (id != last) {  // AudioTargetManager.cs:67-73
     memcpy(t.pos.data() + (size_t)id * 3, t.pos.data() + (size_t)last * 3, 12);
     if (!t.dirty[(size_t)id]) { t.dirty[(size_t)id] = 1; t.dirty_list.push_back(id); }
     t.src[(size_t)id] = t.src[(size_t)last];  // the same target, at a new index
+    if (c->flags & ART_CTX_TARGET_OWNERS_FOLLOW)
+      // swapped.Id.Value = removeIndex (:86) -> AudioCollider.UpdateAudioTargetId (AudioCollider.cs:46-50):
+      // the swapped target's colliders take its new index, as art_collider_set would write them
+      for (int k = 0; k < 3; ++k) {
+        auto& K = c->store.kinds[k];
+        const size_t rs = kRecSize[k], tid_off = kTidOff[k];
+        const int16_t from = (int16_t)last, to = (int16_t)id;
+        for (int i = 0; i < K.count; ++i) {
+          uint8_t* tid = K.recs.data() + (size_t)i * rs + tid_off;
+          if (memcmp(tid, &from, 2) != 0) continue;
+          memcpy(tid, &to, 2);
+          if (!K.dirty[(size_t)i]) { K.dirty[(size_t)i] = 1; K.dirty_list.push_back(i); }
+          t.last_remove_owners[k]++;
+        }
+      }
   }
   t.count = last;
   t.pos.resize((size_t)last * 3);
@@ -778,6 +805,29 @@ ART_API int art_debug_target_sync_map(art_ctx* c, int32_t* src, int32_t cap) {
   const std::vector<int>& m = c->targets.last_map;
   for (int32_t i = 0; i < cap && (size_t)i < m.size(); ++i) src[i] = m[(size_t)i];
   return c->targets.synced;
+}
+
+ART_API int art_target_follow_map(art_ctx* c, int32_t* src, int32_t cap, int32_t* base_count) {
+  if (!c || cap < 0 || (cap > 0 && !src)) return ART_E_INVALID;
+  const TargetStore& t = c->targets;
+  for (int32_t i = 0; i < cap && (size_t)i < t.follow.size(); ++i) src[i] = t.follow[(size_t)i];
+  if (base_count) *base_count = t.base_count;
+  return t.synced;
+}
+
+ART_API int art_target_follow_mark(art_ctx* c) {
+  if (!c) return ART_E_INVALID;
+  TargetStore& t = c->targets;
+  t.follow.resize((size_t)t.synced);
+  for (int i = 0; i < t.synced; ++i) t.follow[(size_t)i] = i;
+  t.base_count = t.synced;
+  return ART_OK;
+}
+
+ART_API int art_target_last_remove_owners(art_ctx* c, int32_t out[3]) {
+  if (!c || !out) return ART_E_INVALID;
+  for (int k = 0; k < 3; ++k) out[k] = c->targets.last_remove_owners[k];
+  return ART_OK;
 }
 
 ART_API int art_collider_add(art_ctx* c, int32_t kind, const void* rec, int32_t* out_id) {

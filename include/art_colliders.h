@@ -168,8 +168,26 @@ ART_API int art_target_set_many(art_ctx* ctx, const int32_t* ids, const float* p
 /* RemoveAudioTargetFromSystem (:59-96): the last position moves to id. An id out of range is
  * skipped (returns ART_OK, nothing changes), as art_collider_remove_swapback does. The colliders
  * owned by the swapped target keep their audio_target_id: re-numbering them (the reference's id
- * pool, :75-86, and the colliders' own updates) stays with the caller, through art_collider_set. */
+ * pool, :75-86, and the colliders' own updates) stays with the caller, through art_collider_set,
+ * unless ART_CTX_TARGET_OWNERS_FOLLOW (below) is set. */
 ART_API int art_target_remove_swapback(art_ctx* ctx, int32_t id);
+
+/* art_set_flags bit (ABI 3.13): art_target_remove_swapback(id) with a valid id that is not the last
+ * index also does what the reference does by itself: swapped.Id.Value = removeIndex
+ * (Audio/AudioTargetManager.cs:86) drives AudioCollider.UpdateAudioTargetId
+ * (Audio/Colliders/AudioCollider.cs:32,46-50), which rewrites AudioTargetId and pushes the collider
+ * through UpdateColiderInSystem. Every record of the collider mirror, of all three kinds, whose
+ * audio_target_id is the last index gets audio_target_id = id, exactly as art_collider_set would write
+ * it: marked dirty, uploaded by the next art_colliders_sync, counted in the owner histogram there.
+ * Records that name the removed id itself are left alone: in the reference they belong to the removed
+ * GameObject and leave through their own OnDisable (the caller removes them, art_collider_remove_swapback).
+ * A remove then dirties both stores; art_targets_sync and art_colliders_sync may follow in either
+ * order, and the frame after both is that of a fresh bind. Without the flag nothing changes. */
+#define ART_CTX_TARGET_OWNERS_FOLLOW 0x1000u
+
+/* Records re-numbered by the most recent art_target_remove_swapback, per kind: spheres, AABBs, OBBs
+ * (all 0 without the flag, for id == last and for an id out of range). */
+ART_API int art_target_last_remove_owners(art_ctx* ctx, int32_t out[3]);
 
 /* positions[id] of the mirror (NextBatch, including unsynced changes). */
 ART_API int art_target_get(art_ctx* ctx, int32_t id, float pos[3]);
@@ -221,10 +239,11 @@ ART_API int art_debug_cells_arena(art_ctx* ctx, uint64_t* used, uint64_t* cap, u
  * What stays with the caller after a count change that kept the scene bound:
  *  - the fan-block stride follows the synced count: re-query art_fan_layout_get with
  *    art_target_synced_count (as after a rebind) and size d_block for it;
- *  - the tick's and the mix's source numbering s = f * T + t changes with T: re-packing d_state
- *    and d_volume for the new numbering;
- *  - re-numbering the audio_target_id of the colliders a swapped target owns (art_collider_set),
- *    as art_target_remove_swapback says. */
+ *  - without ART_CTX_TARGET_OWNERS_FOLLOW: re-numbering the audio_target_id of the colliders a
+ *    swapped target owns (art_collider_set), as art_target_remove_swapback says.
+ * The tick's and the mix's source numbering s = f * T + t changes with T and with every swap-back:
+ * art_dsp_sources_follow_device (art_dsp.h) moves d_state and d_volume to the new numbering on the
+ * device, from the follow map below. */
 ART_API int art_targets_reserve(art_ctx* ctx, int32_t capacity);
 ART_API int art_target_capacity(art_ctx* ctx);          /* the reserved capacity, or < 0 */
 
@@ -244,6 +263,22 @@ ART_API int art_targets_last_resize(art_ctx* ctx, art_target_resize_stats* out);
  * index the same target held before the last art_targets_sync, or -1 if it is new.
  * Returns the synced count. */
 ART_API int art_debug_target_sync_map(art_ctx* ctx, int32_t* src, int32_t cap);
+
+/* ------------------------------------------- per-source data follows the targets (ABI 3.13) */
+
+/* The follow map: the maps of every committed art_targets_sync since the last art_target_follow_mark,
+ * composed. src[i] is the index that the target now at synced index i held in the base list (the
+ * synced list at the mark), or -1 if it was not in it. Before the first mark the base list is empty
+ * (base_count 0), so every target is new. A caller that keeps arrays per source (the tick's d_state and
+ * d_volume, art_dsp_sources_follow_device) or per target moves each of them by this map, then marks;
+ * any number of syncs may lie between two marks.
+ * Returns the synced count; writes min(cap, count) entries; *base_count (may be NULL) = the base
+ * list's length. Host only, no synchronisation, works on the CPU backend. ART_E_INVALID for a NULL
+ * context, cap < 0 or a NULL src with cap > 0. */
+ART_API int art_target_follow_map(art_ctx* ctx, int32_t* src, int32_t cap, int32_t* base_count);
+
+/* The base list becomes the synced list: follow = identity, base_count = synced count. */
+ART_API int art_target_follow_mark(art_ctx* ctx);
 
 #ifdef __cplusplus
 }

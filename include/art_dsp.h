@@ -176,6 +176,59 @@ ART_API int art_dsp_tick_mix_device(art_ctx* ctx, const void* d_block, uint32_t 
 ART_API int art_dsp_mix_host(const art_dsp_source_params* params, art_dsp_state* state, const float* dry,
         int32_t fan_count, int32_t target_count, int32_t frames, float* mix);
 
+/* ---- sources follow the targets (ABI 3.13): d_state / d_volume after a target count change ------- */
+
+/* The tick and the mix number sources s = f*T + t. When T changes, or a swap-back moves the last
+ * target into a hole, every fan's filter states and volumes sit at the wrong index. These two calls
+ * move them to the new numbering, out of place, by a target map (art_target_follow_map,
+ * art_colliders.h) and an optional fan map (listeners that join and leave in the same pass).
+ *
+ * The contract is the host twin, literally. For f < fan_count_new and t < target_count_new:
+ *   s  = f * target_count_new + t
+ *   fo = fan_src ? fan_src[f] : f
+ *   to = target_src[t]
+ *   if 0 <= fo < fan_count_old and 0 <= to < target_count_old:
+ *     state_new[s]  = the 32 bytes of state_old[fo * target_count_old + to], bit for bit
+ *     volume_new[s] = volume_old ? volume_old[fo * target_count_old + to] : new_volume
+ *   else (a new source):
+ *     state_new[s]  = 32 zero bytes (the zero-initialised C# structs)
+ *     volume_new[s] = new_volume
+ * A fan index out of range, on either side, means "new listener" (the device cannot refuse it).
+ * volume_new NULL: no volumes are written. volume_old NULL with volume_new set: every source gets
+ * new_volume. The tick's default for a NULL volume array is 1.0f: that is the usual new_volume.
+ * The old arrays are only read; old and new arrays must not overlap.
+ *
+ * Host twin, context-free: ART_E_INVALID for a negative count; ART_OK with nothing written when
+ * fan_count_new == 0 or target_count_new == 0; otherwise ART_E_INVALID for a NULL target_src or
+ * state_new, a NULL state_old with fan_count_old * target_count_old > 0, or a target_src entry
+ * outside [-1, target_count_old) (checked before anything is written). */
+ART_API int art_dsp_sources_follow_host(const int32_t* target_src, int32_t target_count_new, int32_t target_count_old,
+        const int32_t* fan_src, int32_t fan_count_new, int32_t fan_count_old,
+        const art_dsp_state* state_old, const float* volume_old,
+        art_dsp_state* state_new, float* volume_new, float new_volume);
+
+/* The same on the context's first device, one launch enqueued on `stream`: no synchronisation, no
+ * event, no host round trip (the target map travels in the kernel's argument block; target_src is
+ * read before the call returns). It reads nothing of the scene, so it takes no part in the ordering
+ * of frames and syncs: the caller's stream orders it against the ticks that use the arrays. The arrays
+ * need 4-byte alignment only (16-byte accesses when both state arrays allow them).
+ * target_src NULL = the store's follow map: target_count_new and target_count_old must then equal
+ * art_target_synced_count and the follow map's base count, else ART_E_INVALID (the caller's check
+ * that its idea of T agrees with the store's). With a host target_src the call needs no store and no
+ * bound scene. d_fan_src is a device array int32[fan_count_new], or NULL = identity.
+ * ART_E_INVALID for a negative count, a required pointer that is NULL, a misaligned pointer, an old
+ * array that overlaps a new one (a range check on the host), or a target_src entry outside
+ * [-1, target_count_old). ART_OK and no launch when fan_count_new == 0 or target_count_new == 0.
+ * ART_E_UNSUPPORTED when a target count exceeds the frame limit (256), when
+ * fan_count_new * target_count_new exceeds 2^31 - 1, or on the CPU backend. */
+ART_API int art_dsp_sources_follow_device(art_ctx* ctx,
+        const int32_t* target_src /* host, or NULL = the store's follow map */,
+        int32_t target_count_new, int32_t target_count_old,
+        const int32_t* d_fan_src /* device int32[fan_count_new], or NULL = identity */,
+        int32_t fan_count_new, int32_t fan_count_old,
+        const art_dsp_state* d_state_old, const float* d_volume_old,
+        art_dsp_state* d_state_new, float* d_volume_new, float new_volume, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,9 @@
 
 (The default source holds the raytrace stage; the permeation kernels are a second source, csrc/art_permeate.hip,
 the muffle cell lists and the target syncs' kernels a third, csrc/art_cells.hip: profiles/targets_resize_spill.txt,
-the BVH build, refit and relabel kernels a fourth, csrc/art_bvh.hip: profiles/colliders_resize_spill.txt.)
+the BVH build, refit and relabel kernels a fourth, csrc/art_bvh.hip: profiles/colliders_resize_spill.txt,
+the per-sample DSP, the tick, the mix and dsp_sources_follow_kernel a fifth, csrc/art_dsp.hip:
+profiles/sources_follow_spill.txt.)
 
 For every kernel: its VGPR count, scratch, LDS, occupancy and code length, and for each spill slot the stores and reloads
 with the loop they sit in (the compiler's "Loop Header" / "in Loop" block annotations). A spill
