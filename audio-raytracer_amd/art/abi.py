@@ -72,6 +72,8 @@ ART_DEBUG_BVH_BOUNDS, ART_DEBUG_BVH_NODES = 0, 1
 CULL_REC = np.dtype([("lo", "<f4", 3), ("fscale", "<f4"), ("hi", "<f4", 3), ("factor", "<f4")])
 # art_debug_cells_lists (include/art_device.h): which array of the muffle direction-cell lists
 ART_DEBUG_CELLS_STARTS, ART_DEBUG_CELLS_ENTRIES, ART_DEBUG_CELLS_OK, ART_DEBUG_CELLS_FAR, ART_DEBUG_CELLS_INFO = 0, 1, 2, 3, 4
+# art_debug_last_dsp_kernel (include/art_dsp.h): the kernel the last per-sample DSP call launched
+ART_DSP_KERNEL_NONE, ART_DSP_KERNEL_TILED, ART_DSP_KERNEL_LANE, ART_DSP_KERNEL_MIX = 0, 1, 2, 3
 ART_OUT_HIT_RESULTS = 0x1
 # art_fan.ray_hit_ids: ColliderType (Enums/ColliderType.cs) << 30 | index in that type's array
 ART_COLLIDER_AABB, ART_COLLIDER_OBB, ART_COLLIDER_SPHERE = 1, 2, 3
@@ -259,6 +261,7 @@ SIGNATURES = {
     "art_dsp_source_params_get": (I32, [C.POINTER(art_spatializer_settings), C.POINTER(art_audio_source), I32,
                                         C.POINTER(art_dsp_source_params)]),
     "art_dsp_process_device": (I32, [VP, VP, VP, VP, I32, I32, VP]),
+    "art_debug_last_dsp_kernel": (I32, [VP]),
     "art_fibonacci_directions_device": (I32, [VP, I32, VP, VP]),
     "art_dsp_tick_params_host": (I32, [C.POINTER(art_spatializer_settings), I32, VP, C.POINTER(art_fan), I32, VP, I32, VP,
                                        VP]),

@@ -123,6 +123,22 @@ def source_params(settings: SpatializerSettings, source: AudioSource, sample_rat
     return out
 
 
+def process_device(ctx, d_data, d_params, d_state, count: int, frames: int, stream: int | None = None):
+    """art_dsp_process_device on `stream` (not synchronised): d_data float [count][frames][2], processed
+    in place; buffers are torch tensors or raw device pointers (d_data needs 4-byte alignment only)."""
+    rc = ctx.lib.art_dsp_process_device(ctx.ptr, _dptr(d_data), _dptr(d_params), _dptr(d_state), count, frames, stream)
+    if rc:
+        ctx._raise(rc)
+
+
+def debug_last_dsp_kernel(ctx) -> int:
+    """art_debug_last_dsp_kernel: the abi.ART_DSP_KERNEL_* the context's last per-sample DSP call launched."""
+    rc = ctx.lib.art_debug_last_dsp_kernel(ctx.ptr)
+    if rc < 0:
+        ctx._raise(rc)
+    return rc
+
+
 @dataclass
 class Listener:
     """The AudioListener's transform: position and rotation (quaternion x, y, z, w)."""

@@ -55,8 +55,8 @@ namespace {
 // art_colliders_last_resize); 3.11: art_debug_node_margin_cap; 3.12: art_debug_cells_lists;
 // 3.13: per-source data and collider owners follow the targets (art_target_follow_map, art_target_follow_mark,
 // art_dsp_sources_follow_host, art_dsp_sources_follow_device, ART_CTX_TARGET_OWNERS_FOLLOW,
-// art_target_last_remove_owners)
-constexpr uint32_t kAbiVersion = (3u << 16) | 13u;
+// art_target_last_remove_owners); 3.14: art_debug_last_dsp_kernel, ART_DSP_KERNEL_*
+constexpr uint32_t kAbiVersion = (3u << 16) | 14u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {

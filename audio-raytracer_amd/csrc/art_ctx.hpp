@@ -263,6 +263,7 @@ struct art_ctx {
   uint32_t flags = 0;
   art::HostBuf h_in, h_block;
   art::HostBuf h_dsp;            // staging of art_dsp_process
+  int last_dsp_kernel = 0;       // ART_DSP_KERNEL_* of the last per-sample DSP call (art_debug_last_dsp_kernel)
   // the audio tick's spatializer settings (art_dsp_settings_bind): the scalars, the curves pointing
   // into devs[0].tick_curves
   struct TickSettings {

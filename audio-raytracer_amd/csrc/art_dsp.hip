@@ -431,13 +431,14 @@ void dsp_mix_host(const art_dsp_source_params* params, art_dsp_state* state, con
   }
 }
 
-void launch_dsp_mix(const float* dry, const art_dsp_source_params* params, art_dsp_state* state, int fan_count, int T,
-                    int frames, float* mix, hipStream_t st) {
-  if (fan_count <= 0 || T <= 0 || frames <= 0) return;
+int launch_dsp_mix(const float* dry, const art_dsp_source_params* params, art_dsp_state* state, int fan_count, int T,
+                   int frames, float* mix, hipStream_t st) {
+  if (fan_count <= 0 || T <= 0 || frames <= 0) return ART_DSP_KERNEL_NONE;
   const int G = T <= kTS ? kTS / T : 1;
   hipLaunchKernelGGL(dsp_mix_kernel, dim3((fan_count + G - 1) / G), dim3(64), 0, st, dry, params, state, mix, fan_count,
                      T, frames, (uint32_t)((unsigned long long)T * frames * 8ull),
                      (uint32_t)((unsigned long long)fan_count * frames * 8ull));
+  return ART_DSP_KERNEL_MIX;
 }
 
 
@@ -592,9 +593,10 @@ void launch_dsp_sources_follow(const DspFollowArgs& a, hipStream_t st) {
                      dim3(kFollowBlock), 0, st, a);
 }
 
-void launch_dsp(float* data, unsigned long long data_bytes, const long long* offsets, const int* frames_of,
-                int frames_all, const art_dsp_source_params* params, art_dsp_state* state, int count, hipStream_t st) {
-  if (count <= 0) return;
+// Returns the kernel it launched (ART_DSP_KERNEL_*, art_debug_last_dsp_kernel).
+int launch_dsp(float* data, unsigned long long data_bytes, const long long* offsets, const int* frames_of,
+               int frames_all, const art_dsp_source_params* params, art_dsp_state* state, int count, hipStream_t st) {
+  if (count <= 0) return ART_DSP_KERNEL_NONE;
   static const int mode = [] {  // ART_DSP_KERNEL=lane: one lane per source, direct loads (A/B only)
     const char* e = std::getenv("ART_DSP_KERNEL");
     return e && !std::strcmp(e, "lane") ? 1 : 0;
@@ -605,10 +607,11 @@ void launch_dsp(float* data, unsigned long long data_bytes, const long long* off
   if (mode == 0 && aligned && data_bytes < 0x7fffffffULL) {
     hipLaunchKernelGGL(dsp_tiled_kernel, dim3((count + kTS - 1) / kTS), dim3(64), 0, st, data, offsets, frames_of,
                        frames_all, params, state, count, (uint32_t)data_bytes);
-  } else {
-    hipLaunchKernelGGL(dsp_kernel, dim3((count + kDspBlock - 1) / kDspBlock), dim3(kDspBlock), 0, st, data, offsets,
-                       frames_of, frames_all, params, state, count);
+    return ART_DSP_KERNEL_TILED;
   }
+  hipLaunchKernelGGL(dsp_kernel, dim3((count + kDspBlock - 1) / kDspBlock), dim3(kDspBlock), 0, st, data, offsets,
+                     frames_of, frames_all, params, state, count);
+  return ART_DSP_KERNEL_LANE;
 }
 
 }  // namespace art

@@ -18,6 +18,7 @@ ART_API int art_dsp_process(art_ctx* c, const art_spatializer_settings* settings
   if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
   if (!settings || count < 0 || (count > 0 && !sources) || sample_rate <= 0) return fail(c, ART_E_INVALID, "invalid argument");
   if (c->inflight) return fail(c, ART_E_STATE, "a frame is in flight");
+  c->last_dsp_kernel = ART_DSP_KERNEL_NONE;
   // host: per-buffer scalars; stereo sources with samples go to the device
   std::vector<int> idx;
   std::vector<art_dsp_source_params> params;
@@ -75,9 +76,10 @@ ART_API int art_dsp_process(art_ctx* c, const art_spatializer_settings* settings
   std::memcpy(h + o_params, params.data(), n * sizeof(art_dsp_source_params));
   uint8_t* d = static_cast<uint8_t*>(dv.dsp.p);
   HIP_TRY(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, dv.stream));
-  launch_dsp(reinterpret_cast<float*>(d + o_data), (unsigned long long)total * 4, reinterpret_cast<const long long*>(d + o_offs),
-             reinterpret_cast<const int*>(d + o_frames), 0, reinterpret_cast<const art_dsp_source_params*>(d + o_params),
-             reinterpret_cast<art_dsp_state*>(d + o_state), (int)n, dv.stream);
+  c->last_dsp_kernel = launch_dsp(reinterpret_cast<float*>(d + o_data), (unsigned long long)total * 4,
+                                  reinterpret_cast<const long long*>(d + o_offs), reinterpret_cast<const int*>(d + o_frames), 0,
+                                  reinterpret_cast<const art_dsp_source_params*>(d + o_params),
+                                  reinterpret_cast<art_dsp_state*>(d + o_state), (int)n, dv.stream);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(h + o_data, d + o_data, (size_t)total * 4, hipMemcpyDeviceToHost, dv.stream));
   HIP_TRY(c, hipMemcpyAsync(h + o_state, d + o_state, n * sizeof(art_dsp_state), hipMemcpyDeviceToHost, dv.stream));
@@ -95,11 +97,12 @@ ART_API int art_dsp_process_device(art_ctx* c, float* d_data, const art_dsp_sour
   if (!c) return ART_E_INVALID;
   if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
   if (count < 0 || frames < 0 || (count > 0 && (!d_data || !d_params || !d_state))) return fail(c, ART_E_INVALID, "invalid argument");
+  c->last_dsp_kernel = ART_DSP_KERNEL_NONE;
   if (count == 0 || frames == 0) return ART_OK;
   Device& dv = c->devs[0];
   HIP_TRY(c, hipSetDevice(dv.id));
-  launch_dsp(d_data, (unsigned long long)count * (unsigned long long)frames * 8ull, nullptr, nullptr, frames, d_params,
-             d_state, count, static_cast<hipStream_t>(stream));
+  c->last_dsp_kernel = launch_dsp(d_data, (unsigned long long)count * (unsigned long long)frames * 8ull, nullptr, nullptr,
+                                  frames, d_params, d_state, count, static_cast<hipStream_t>(stream));
   HIP_TRY(c, hipGetLastError());
   return ART_OK;
 }
@@ -226,9 +229,11 @@ ART_API int art_dsp_tick_device(art_ctx* c, const void* d_block, uint32_t out_fl
   int count = 0;
   int rc = tick_params(c, __func__, d_block, out_flags, fan_count, d_listeners, d_volume, d_params,
                        frames > 0 && (!d_data || !d_state), st, count);
-  if (rc || count == 0 || frames == 0) return rc;
-  launch_dsp(d_data, (unsigned long long)count * (unsigned long long)frames * 8ull, nullptr, nullptr, frames, d_params,
-             d_state, count, st);
+  if (rc) return rc;
+  c->last_dsp_kernel = ART_DSP_KERNEL_NONE;
+  if (count == 0 || frames == 0) return ART_OK;
+  c->last_dsp_kernel = launch_dsp(d_data, (unsigned long long)count * (unsigned long long)frames * 8ull, nullptr, nullptr,
+                                  frames, d_params, d_state, count, st);
   HIP_TRY(c, hipGetLastError());
   return ART_OK;
 }
@@ -240,6 +245,7 @@ ART_API int art_dsp_mix_device(art_ctx* c, const float* d_dry, const art_dsp_sou
   if (!c) return ART_E_INVALID;
   if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
   if (fan_count < 0 || target_count < 0 || frames < 0) return fail(c, ART_E_INVALID, "%s: negative argument", __func__);
+  c->last_dsp_kernel = ART_DSP_KERNEL_NONE;
   if (fan_count == 0 || frames == 0) return ART_OK;
   if (target_count < 1) return fail(c, ART_E_INVALID, "%s: target_count must be at least 1", __func__);
   if (!d_dry || !d_params || !d_state || !d_mix) return fail(c, ART_E_INVALID, "%s: bad device buffers", __func__);
@@ -247,7 +253,8 @@ ART_API int art_dsp_mix_device(art_ctx* c, const float* d_dry, const art_dsp_sou
   if (int rc = mix_limits(d_dry, d_mix, fan_count, target_count, frames, why)) return fail(c, rc, "%s: %s", __func__, why);
   Device& dv = c->devs[0];
   HIP_TRY(c, hipSetDevice(dv.id));
-  launch_dsp_mix(d_dry, d_params, d_state, fan_count, target_count, frames, d_mix, static_cast<hipStream_t>(stream));
+  c->last_dsp_kernel =
+      launch_dsp_mix(d_dry, d_params, d_state, fan_count, target_count, frames, d_mix, static_cast<hipStream_t>(stream));
   HIP_TRY(c, hipGetLastError());
   return ART_OK;
 }
@@ -262,8 +269,10 @@ ART_API int art_dsp_tick_mix_device(art_ctx* c, const void* d_block, uint32_t ou
   const TickMix mix{d_dry, d_mix, frames};
   int rc = tick_params(c, __func__, d_block, out_flags, fan_count, d_listeners, d_volume, d_params,
                        frames > 0 && (!d_dry || !d_state || !d_mix), st, count, &mix);
-  if (rc || count == 0 || frames == 0) return rc;
-  launch_dsp_mix(d_dry, d_params, d_state, fan_count, c->fr.T, frames, d_mix, st);
+  if (rc) return rc;
+  c->last_dsp_kernel = ART_DSP_KERNEL_NONE;
+  if (count == 0 || frames == 0) return ART_OK;
+  c->last_dsp_kernel = launch_dsp_mix(d_dry, d_params, d_state, fan_count, c->fr.T, frames, d_mix, st);
   HIP_TRY(c, hipGetLastError());
   return ART_OK;
 }
@@ -275,6 +284,12 @@ ART_API int art_dsp_mix_host(const art_dsp_source_params* params, art_dsp_state*
   if (target_count < 1 || !params || !state || !dry || !mix) return ART_E_INVALID;
   dsp_mix_host(params, state, dry, fan_count, target_count, frames, mix);
   return ART_OK;
+}
+
+ART_API int art_debug_last_dsp_kernel(art_ctx* c) {
+  if (!c) return ART_E_INVALID;
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
+  return c->last_dsp_kernel;
 }
 
 // ---------------------------------------------------------------------------- sources follow the targets

@@ -160,8 +160,9 @@ struct SortBufs {
 // per-sample spatializer DSP (art_dsp.hip)
 int dsp_source_params(const art_spatializer_settings& st, const art_audio_source& src, int sample_rate,
                       art_dsp_source_params& p);
-void launch_dsp(float* data, unsigned long long data_bytes, const long long* offsets, const int* frames_of,
-                int frames_all, const art_dsp_source_params* params, art_dsp_state* state, int count, hipStream_t st);
+// (returns the kernel it launched, ART_DSP_KERNEL_*: art_debug_last_dsp_kernel)
+int launch_dsp(float* data, unsigned long long data_bytes, const long long* offsets, const int* frames_of,
+               int frames_all, const art_dsp_source_params* params, art_dsp_state* state, int count, hipStream_t st);
 // The audio tick's parameter step (art_dsp_tick_*): source s = f * T + t reads the settings record at
 // block + f * stride + settings_off + 24 t, listeners[f], targets[3 t ..] and volume[s] (or 1).
 int dsp_tick_params_host(const art_spatializer_settings& st, int sample_rate, const art_listener* listeners,
@@ -183,8 +184,8 @@ void launch_dsp_tick_params(const DspTickArgs& a, hipStream_t st);
 // The device form needs 8-B aligned dry / mix and T * frames * 8, fan_count * frames * 8 < 2^31.
 void dsp_mix_host(const art_dsp_source_params* params, art_dsp_state* state, const float* dry, int fan_count, int T,
                   int frames, float* mix);
-void launch_dsp_mix(const float* dry, const art_dsp_source_params* params, art_dsp_state* state, int fan_count, int T,
-                    int frames, float* mix, hipStream_t st);
+int launch_dsp_mix(const float* dry, const art_dsp_source_params* params, art_dsp_state* state, int fan_count, int T,
+                   int frames, float* mix, hipStream_t st);  // returns ART_DSP_KERNEL_MIX, or _NONE for an empty call
 // Sources follow the targets (art_dsp_sources_follow_*): state_new / volume_new [count = F_new * T_new]
 // gathered from the old arrays by target_src (in the argument block: T <= kMaxTargets) and fan_src.
 struct DspFollowArgs {

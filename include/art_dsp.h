@@ -106,6 +106,19 @@ ART_API int art_dsp_source_params_get(const art_spatializer_settings* settings, 
 ART_API int art_dsp_process_device(art_ctx* ctx, float* d_data, const art_dsp_source_params* d_params,
                                    art_dsp_state* d_state, int32_t count, int32_t frames, void* stream);
 
+/* Diagnostics (tests, ABI 3.14): the kernel the context's last per-sample DSP call launched, so a
+ * test knows which kernel it compared (art_dsp_process, art_dsp_process_device and art_dsp_tick_device
+ * pick the tiled kernel, or the lane kernel when d_data is not 8-byte aligned, the batch reaches
+ * 2^31 - 1 bytes, or ART_DSP_KERNEL=lane is set in the environment; the listener mix has one kernel).
+ * ART_DSP_KERNEL_NONE before the first call and after a call that had nothing to launch. A host-side
+ * decision: it does not synchronise. ART_E_INVALID for a NULL context, ART_E_UNSUPPORTED on the CPU
+ * backend. */
+#define ART_DSP_KERNEL_NONE  0
+#define ART_DSP_KERNEL_TILED 1   /* dsp_tiled_kernel: one lane per (source, channel), tiles through LDS */
+#define ART_DSP_KERNEL_LANE  2   /* dsp_kernel: one lane per source, direct loads */
+#define ART_DSP_KERNEL_MIX   3   /* dsp_mix_kernel: the listener mix */
+ART_API int art_debug_last_dsp_kernel(art_ctx* ctx);
+
 /* ---- audio tick (ABI 3.5): spatializer parameters from a frame's result blocks ---------------- */
 
 /* The AudioListener's transform (one per fan): position, rotation as a quaternion (x, y, z, w). */

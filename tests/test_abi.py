@@ -27,7 +27,7 @@ def test_headers_declare_expected_surface():
     names = declared_symbols()
     for n in ("art_create", "art_schedule", "art_is_completed", "art_complete", "art_destroy", "art_last_error",
               "art_scene_bind", "art_launch_device", "art_synth_scene", "art_debug_leaf_order", "art_debug_last_plan",
-              "art_debug_bvh_records", "art_debug_cells_lists"):
+              "art_debug_bvh_records", "art_debug_cells_lists", "art_debug_last_dsp_kernel"):
         assert n in names
 
 
@@ -80,8 +80,25 @@ def test_version():
     v = art.load_library().art_version()
     # 3.0: art_kernel_times per kernel family (a grown struct: major bump); 3.1: ART_CTX_EVENT_EACH_LAUNCH,
     # art_recip_exact_device; 3.2: art_debug_last_plan, ART_PLAN_*; 3.9: art_debug_bvh_records;
-    # 3.12: art_debug_cells_lists
-    assert v >> 16 == 3 and (v & 0xffff) >= 12
+    # 3.12: art_debug_cells_lists; 3.14: art_debug_last_dsp_kernel
+    assert v >> 16 == 3 and (v & 0xffff) >= 14
+
+
+def test_dsp_kernel_hook_without_device():
+    """art_debug_last_dsp_kernel (ABI 3.14): the binding's ART_DSP_KERNEL_* values are the header's, and
+    the CPU backend (no kernels) refuses the query."""
+    hdr = open(os.path.join(ROOT, "include", "art_dsp.h")).read()
+    in_hdr = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define (ART_DSP_KERNEL_\w+)\s+(\d+)\b", hdr)}
+    assert in_hdr == {"ART_DSP_KERNEL_NONE": 0, "ART_DSP_KERNEL_TILED": 1, "ART_DSP_KERNEL_LANE": 2, "ART_DSP_KERNEL_MIX": 3}
+    for name, v in in_hdr.items():
+        assert getattr(abi, name) == v
+    assert art.load_library().art_debug_last_dsp_kernel(None) == abi.ART_E_INVALID
+    with art.Context(0) as cpu:
+        assert cpu.lib.art_debug_last_dsp_kernel(cpu.ptr) == abi.ART_E_UNSUPPORTED
+        assert "CPU backend" in cpu.lib.art_last_error(cpu.ptr).decode()
+        with pytest.raises(art.ArtError) as e:
+            art.dsp.debug_last_dsp_kernel(cpu)
+        assert e.value.code == abi.ART_E_UNSUPPORTED
 
 
 def test_cells_lists_hook_without_device():
