@@ -266,6 +266,11 @@ SIGNATURES = {
     "art_dsp_tick_params_host": (I32, [C.POINTER(art_spatializer_settings), I32, VP, C.POINTER(art_fan), I32, VP, I32, VP,
                                        VP]),
     "art_dsp_settings_bind": (I32, [VP, C.POINTER(art_spatializer_settings), I32]),
+    "art_dsp_tick_params_classes_host": (I32, [VP, I32, I32, VP, C.POINTER(art_fan), I32, VP, I32, VP, VP, VP]),
+    "art_dsp_settings_bind_classes": (I32, [VP, VP, I32, I32]),
+    "art_dsp_target_classes_set": (I32, [VP, VP, I32]),
+    "art_dsp_target_classes_get": (I32, [VP, VP, I32]),
+    "art_dsp_target_classes_follow": (I32, [VP, VP, I32, I32, C.c_uint8]),
     "art_dsp_tick_params_device": (I32, [VP, VP, U32, I32, VP, VP, VP, VP]),
     "art_dsp_tick_device": (I32, [VP, VP, U32, I32, VP, VP, VP, VP, I32, VP, VP]),
     "art_dsp_mix_device": (I32, [VP, VP, VP, VP, I32, I32, I32, VP, VP]),

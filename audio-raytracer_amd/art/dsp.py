@@ -16,6 +16,11 @@ in ascending target order (include/art_dsp.h has the contract).
 
 sources_follow_device / sources_follow_host move the per-source filter states and volumes to the new
 numbering s = f * T + t after targets were added or removed (TargetStore.follow_map, art/targets.py).
+
+Settings per target (bind_settings_classes, set_target_classes / get_target_classes,
+follow_target_classes, tick_params_classes_host): every AudioSpatializer carries its own settings
+(AudioSpatializer.cs:10-11), so a context binds a table of settings classes and a class map names each
+target's class; the tick entry points then evaluate source f * T + t with classes[map[t]].
 """
 from __future__ import annotations
 
@@ -198,6 +203,87 @@ def bind_settings(ctx, settings: SpatializerSettings, sample_rate: int = 48000):
     """art_dsp_settings_bind: the spatializer settings of the later ticks (curves uploaded once)."""
     st = settings.to_c()
     rc = ctx.lib.art_dsp_settings_bind(ctx.ptr, C.byref(st), sample_rate)
+    if rc:
+        ctx._raise(rc)
+
+
+def settings_table(classes):
+    """SpatializerSettings objects as one art_spatializer_settings array (which keeps the curves alive)."""
+    arr = (abi.art_spatializer_settings * max(1, len(classes)))()
+    arr._curves = []
+    for k, s in enumerate(classes):
+        arr[k] = s.to_c()
+        arr._curves.append((s._mc, s._rc))
+    return arr
+
+
+def tick_params_classes_host(classes, listeners, fan_settings: np.ndarray, target_positions: np.ndarray,
+                             target_class=None, volume: np.ndarray | None = None, sample_rate: int = 48000) -> np.ndarray:
+    """art_dsp_tick_params_classes_host: tick_params_host with one SpatializerSettings per class and
+    target_class (uint8 [T], None = every target is class 0) naming each target's class."""
+    fs = np.ascontiguousarray(fan_settings)
+    assert fs.dtype == abi.SETTINGS and fs.ndim == 2
+    S, T = fs.shape
+    ls = listeners_array(listeners)
+    assert ls.size == S
+    tp = np.ascontiguousarray(target_positions, np.float32).reshape(-1, 3)
+    assert tp.shape[0] == T
+    fans = (abi.art_fan * max(S, 1))()
+    for i in range(S):
+        fans[i].settings = fs[i].ctypes.data
+    cls = None
+    if target_class is not None:
+        cls = np.ascontiguousarray(target_class, np.uint8).reshape(-1)
+        assert cls.size == T
+    vol = None
+    if volume is not None:
+        vol = np.ascontiguousarray(volume, np.float32).reshape(-1)
+        assert vol.size == S * T
+    out = np.zeros(S * T, abi.DSP_SOURCE_PARAMS)
+    table = settings_table(classes)
+    rc = abi.load_library().art_dsp_tick_params_classes_host(
+        table, len(classes), sample_rate, ls.ctypes.data, fans, S, tp.ctypes.data, T,
+        cls.ctypes.data if cls is not None else None, vol.ctypes.data if vol is not None else None, out.ctypes.data)
+    if rc:
+        raise ValueError(f"art_dsp_tick_params_classes_host: {abi.ERROR_NAMES.get(rc, rc)}")
+    return out
+
+
+def bind_settings_classes(ctx, classes, sample_rate: int = 48000):
+    """art_dsp_settings_bind_classes: one SpatializerSettings per class (table and curves uploaded once);
+    the later ticks evaluate target t with classes[class map[t]] (set_target_classes)."""
+    table = settings_table(classes)
+    rc = ctx.lib.art_dsp_settings_bind_classes(ctx.ptr, table, len(classes), sample_rate)
+    if rc:
+        ctx._raise(rc)
+
+
+def set_target_classes(ctx, target_class):
+    """art_dsp_target_classes_set: the class of every target (uint8 [T]); empty = every target is class 0."""
+    cls = np.ascontiguousarray(target_class, np.uint8).reshape(-1)
+    rc = ctx.lib.art_dsp_target_classes_set(ctx.ptr, cls.ctypes.data if cls.size else None, cls.size)
+    if rc:
+        ctx._raise(rc)
+
+
+def get_target_classes(ctx) -> np.ndarray:
+    """art_dsp_target_classes_get: the class map, uint8 [count]."""
+    out = np.zeros(256, np.uint8)
+    n = ctx.lib.art_dsp_target_classes_get(ctx.ptr, out.ctypes.data, out.size)
+    if n < 0:
+        ctx._raise(n)
+    return out[:n].copy()
+
+
+def follow_target_classes(ctx, target_src, target_count_new: int, target_count_old: int, new_class: int = 0):
+    """art_dsp_target_classes_follow: the class map moved to the new target numbering, new targets in
+    new_class. target_src is a host int32 array, or None = the store's follow map. Before follow_mark."""
+    ts = None
+    if target_src is not None:
+        ts = np.ascontiguousarray(target_src, np.int32).reshape(-1)
+        assert ts.size == target_count_new
+    rc = ctx.lib.art_dsp_target_classes_follow(ctx.ptr, None if ts is None else ts.ctypes.data, target_count_new,
+                                               target_count_old, new_class)
     if rc:
         ctx._raise(rc)
 

@@ -55,8 +55,10 @@ namespace {
 // art_colliders_last_resize); 3.11: art_debug_node_margin_cap; 3.12: art_debug_cells_lists;
 // 3.13: per-source data and collider owners follow the targets (art_target_follow_map, art_target_follow_mark,
 // art_dsp_sources_follow_host, art_dsp_sources_follow_device, ART_CTX_TARGET_OWNERS_FOLLOW,
-// art_target_last_remove_owners); 3.14: art_debug_last_dsp_kernel, ART_DSP_KERNEL_*
-constexpr uint32_t kAbiVersion = (3u << 16) | 14u;
+// art_target_last_remove_owners); 3.14: art_debug_last_dsp_kernel, ART_DSP_KERNEL_*; 3.15: spatializer
+// settings per target (art_dsp_settings_bind_classes, art_dsp_target_classes_set / _get / _follow,
+// art_dsp_tick_params_classes_host)
+constexpr uint32_t kAbiVersion = (3u << 16) | 15u;
 
 // Per-type sum over targets of colliders NOT owned by the target (permeation loss test counts).
 void count_nonowned(art_ctx* c, const art_frame_desc* d) {

@@ -168,7 +168,7 @@ struct Device {
   bool cells_partial = false;  // a target's lists were rebuilt on their own since the last full build: the arena holds garbage
   DevBuf pairs; // global visibility pairs of the split raytrace path
   DevBuf dsp;   // per-sample DSP batch (art_dsp_process): samples, offsets, frames, params, states
-  DevBuf tick_curves;  // the baked curves of the bound spatializer settings (art_dsp_settings_bind): muffle | reverb volume
+  DevBuf tick_curves;  // the bound spatializer settings (art_dsp_settings_bind*): the class table | each class's baked curves (muffle, reverb volume)
   StoreDev store;
   LaunchFence fence;
   uint64_t exec_launches = 0;
@@ -264,12 +264,17 @@ struct art_ctx {
   art::HostBuf h_in, h_block;
   art::HostBuf h_dsp;            // staging of art_dsp_process
   int last_dsp_kernel = 0;       // ART_DSP_KERNEL_* of the last per-sample DSP call (art_debug_last_dsp_kernel)
-  // the audio tick's spatializer settings (art_dsp_settings_bind): the scalars, the curves pointing
-  // into devs[0].tick_curves
+  // the audio tick's spatializer settings (art_dsp_settings_bind, art_dsp_settings_bind_classes):
+  // class 0's scalars with its curves pointing into devs[0].tick_curves, where the table of all
+  // class_count records lies too (d_table); target_class is the class map (art_dsp_target_classes_*:
+  // host state, empty = every target is class 0, untouched by a bind)
   struct TickSettings {
     bool bound = false;
     art_spatializer_settings st{};
     int sample_rate = 0;
+    int class_count = 0;
+    const art_spatializer_settings* d_table = nullptr;
+    std::vector<uint8_t> target_class;
   } tick;
   art::Frame fr;                 // frame of the bound scene / last schedule
   // in-flight frame

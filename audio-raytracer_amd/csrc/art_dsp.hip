@@ -488,6 +488,31 @@ int dsp_tick_params_host(const art_spatializer_settings& st, int sample_rate, co
   return ART_OK;
 }
 
+// Settings per target: what dsp_tick_params_host writes for a source when it is given
+// settings[cls[t]] as its single settings. Everything is checked before anything is written.
+int dsp_tick_params_classes_host(const art_spatializer_settings* settings, int class_count, int sample_rate,
+                                 const art_listener* listeners, const art_fan* fans, int fan_count, const float* targets,
+                                 int T, const uint8_t* cls, const float* volume, art_dsp_source_params* out) {
+  if (class_count < 1 || class_count > kMaxSettingsClasses) return ART_E_INVALID;
+  for (int k = 0; k < class_count; ++k)
+    if (!curve_ok(settings[k].reverb_volume_curve) || !curve_ok(settings[k].muffle_curve)) return ART_E_INVALID;
+  if (cls)
+    for (int t = 0; t < T; ++t)
+      if (cls[t] >= class_count) return ART_E_INVALID;
+  for (int f = 0; f < fan_count; ++f)
+    if (!fans[f].settings) return ART_E_INVALID;
+  for (int f = 0; f < fan_count; ++f) {
+    for (int t = 0; t < T; ++t) {
+      float rec[6];
+      std::memcpy(rec, &fans[f].settings[t], sizeof rec);
+      const size_t s = (size_t)f * T + t;
+      out[s] = tick_source(settings[cls ? cls[t] : 0], (float)sample_rate, rec, listeners[f],
+                           mk3(targets[3 * t], targets[3 * t + 1], targets[3 * t + 2]), volume ? volume[s] : 1.0f);
+    }
+  }
+  return ART_OK;
+}
+
 namespace {
 
 // The audio tick's parameter step, one lane per source s = f * T + t: the settings record of the
@@ -519,11 +544,52 @@ __global__ __launch_bounds__(kDspBlock) void dsp_tick_params_kernel(DspTickArgs 
   a.out[s] = tick_source(a.st, a.sr, rec, l, target, a.volume ? a.volume[s] : 1.0f);
 }
 
+// The 24-B settings record at rp as six floats (aligned to 4 bytes only, as in dsp_tick_params_kernel).
+__device__ __forceinline__ void load_settings_record(const uint8_t* rp, float rec[6]) {
+  if ((reinterpret_cast<uintptr_t>(rp) & 7) == 0) {
+    const float2* r2 = reinterpret_cast<const float2*>(rp);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float2 v = r2[k];
+      rec[2 * k] = v.x;
+      rec[2 * k + 1] = v.y;
+    }
+  } else {
+    const float* r1 = reinterpret_cast<const float*>(rp);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rec[k] = r1[k];
+  }
+}
+
+// The parameter step with settings per target: one lane per source s = f * T + t, exactly as in
+// dsp_tick_params_kernel, but each lane gathers the record of its target's class from the bound table
+// (a.cls, the class map, lies in the argument block: stream-ordered with the launch). Measured against
+// one wave per (target, 64 fans) with the class's record in SGPRs: DESIGN.md 3a.
+__global__ __launch_bounds__(kDspBlock) void dsp_tick_params_classes_kernel(DspTickClassArgs a) {
+  const long long s64 = (long long)blockIdx.x * kDspBlock + threadIdx.x;
+  if (s64 >= (long long)a.fan_count * a.T) return;
+  const int s = (int)s64;
+  const int f = s / a.T, t = s - f * a.T;
+  float rec[6];
+  load_settings_record(a.block + (size_t)f * a.stride + a.settings_off + (size_t)t * sizeof(art_target_settings), rec);
+  const art_listener l = a.listeners[f];
+  const vec3 target = mk3(a.targets[3 * t], a.targets[3 * t + 1], a.targets[3 * t + 2]);
+  const art_spatializer_settings st = a.table[a.cls[t]];
+  a.out[s] = tick_source(st, a.sr, rec, l, target, a.volume ? a.volume[s] : 1.0f);
+}
+
 }  // namespace
 
 void launch_dsp_tick_params(const DspTickArgs& a, hipStream_t st) {
   if (a.count <= 0) return;
   hipLaunchKernelGGL(dsp_tick_params_kernel, dim3((a.count + kDspBlock - 1) / kDspBlock), dim3(kDspBlock), 0, st, a);
+}
+
+void launch_dsp_tick_params_classes(const DspTickClassArgs& a, hipStream_t st) {
+  if (a.fan_count <= 0 || a.T <= 0) return;
+  const long long count = (long long)a.fan_count * a.T;  // <= 2^31 - 1 (the caller's check)
+  hipLaunchKernelGGL(dsp_tick_params_classes_kernel, dim3((unsigned)((count + kDspBlock - 1) / kDspBlock)), dim3(kDspBlock), 0,
+                     st, a);
 }
 
 // Sources follow the targets: the contract of art_dsp_sources_follow_host, literally.

@@ -117,33 +117,89 @@ ART_API int art_dsp_tick_params_host(const art_spatializer_settings* settings, i
   return dsp_tick_params_host(*settings, sample_rate, listeners, fans, fan_count, target_positions, target_count, volume, out);
 }
 
-ART_API int art_dsp_settings_bind(art_ctx* c, const art_spatializer_settings* settings, int32_t sample_rate) {
+ART_API int art_dsp_tick_params_classes_host(const art_spatializer_settings* settings, int32_t class_count, int32_t sample_rate,
+                                             const art_listener* listeners, const art_fan* fans, int32_t fan_count,
+                                             const float* target_positions, int32_t target_count, const uint8_t* target_class,
+                                             const float* volume, art_dsp_source_params* out) {
+  if (!settings || sample_rate <= 0 || fan_count < 0 || target_count < 0) return ART_E_INVALID;
+  if (fan_count > 0 && (!listeners || !fans || (target_count > 0 && (!target_positions || !out)))) return ART_E_INVALID;
+  return dsp_tick_params_classes_host(settings, class_count, sample_rate, listeners, fans, fan_count, target_positions,
+                                      target_count, target_class, volume, out);
+}
+
+// The bind of class_count settings records (art_dsp_settings_bind: one): the table and every class's
+// two curves as one packed image, [records | curves], in one copy to devs[0].tick_curves.
+static int bind_settings(art_ctx* c, const char* fn, const art_spatializer_settings* settings, int32_t class_count,
+                         int32_t sample_rate) {
   if (!c) return ART_E_INVALID;
-  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", __func__);
+  if (c->cpu) return fail(c, ART_E_UNSUPPORTED, "%s: the CPU backend (device_mask 0) has the host entry points only", fn);
   if (!settings || sample_rate <= 0) return fail(c, ART_E_INVALID, "invalid argument");
-  const art_curve& mc = settings->muffle_curve;
-  const art_curve& rc = settings->reverb_volume_curve;
-  if (!mc.baked || mc.sample_count < 2 || !rc.baked || rc.sample_count < 2)
-    return fail(c, ART_E_INVALID, "art_dsp_settings_bind: both curves need a baked table of at least 2 samples");
+  if (class_count < 1 || class_count > kMaxSettingsClasses)
+    return fail(c, ART_E_INVALID, "%s: class_count %d is outside [1, %d]", fn, class_count, kMaxSettingsClasses);
+  size_t floats = 0;
+  for (int32_t k = 0; k < class_count; ++k) {
+    const art_curve& mc = settings[k].muffle_curve;
+    const art_curve& rc = settings[k].reverb_volume_curve;
+    if (!mc.baked || mc.sample_count < 2 || !rc.baked || rc.sample_count < 2)
+      return fail(c, ART_E_INVALID, "%s: both curves need a baked table of at least 2 samples", fn);
+    floats += (size_t)mc.sample_count + (size_t)rc.sample_count;
+  }
   if (c->inflight) return fail(c, ART_E_STATE, "a frame is in flight");
   if (c->devs.empty()) return fail(c, ART_E_STATE, "the context has no device");
   Device& dv = c->devs[0];
   HIP_TRY(c, hipSetDevice(dv.id));
-  // a tick still running on the caller's stream reads the curves being replaced
+  // a tick still running on the caller's stream reads the table and the curves being replaced
   if (int rc2 = dv.fence.wait(c, dv.stream)) return rc2;
   HIP_TRY(c, hipStreamSynchronize(dv.stream));
   c->tick.bound = false;
-  const size_t nm = (size_t)mc.sample_count, nr = (size_t)rc.sample_count;
-  if (!dv.tick_curves.reserve((nm + nr) * sizeof(float))) return fail(c, ART_E_NOMEM, "device allocation failed");
-  float* d = static_cast<float*>(dv.tick_curves.p);
-  HIP_TRY(c, hipMemcpy(d, mc.baked, nm * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(d + nm, rc.baked, nr * sizeof(float), hipMemcpyHostToDevice));
-  c->tick.st = *settings;
-  c->tick.st.muffle_curve.baked = d;
-  c->tick.st.reverb_volume_curve.baked = d + nm;
+  const size_t table_bytes = (size_t)class_count * sizeof(art_spatializer_settings);  // a multiple of 8
+  const size_t bytes = table_bytes + floats * sizeof(float);
+  if (!dv.tick_curves.reserve(bytes)) return fail(c, ART_E_NOMEM, "device allocation failed");
+  uint8_t* d = static_cast<uint8_t*>(dv.tick_curves.p);
+  std::vector<uint8_t> image(bytes);
+  art_spatializer_settings* table = reinterpret_cast<art_spatializer_settings*>(image.data());
+  size_t at = table_bytes;
+  for (int32_t k = 0; k < class_count; ++k) {
+    table[k] = settings[k];
+    for (art_curve* cv : {&table[k].muffle_curve, &table[k].reverb_volume_curve}) {
+      const size_t n = (size_t)cv->sample_count * sizeof(float);
+      std::memcpy(image.data() + at, cv->baked, n);
+      cv->baked = reinterpret_cast<float*>(d + at);
+      at += n;
+    }
+  }
+  HIP_TRY(c, hipMemcpy(d, image.data(), bytes, hipMemcpyHostToDevice));
+  c->tick.st = table[0];
+  c->tick.class_count = class_count;
+  c->tick.d_table = reinterpret_cast<const art_spatializer_settings*>(d);
   c->tick.sample_rate = sample_rate;
   c->tick.bound = true;
   return ART_OK;
+}
+
+ART_API int art_dsp_settings_bind(art_ctx* c, const art_spatializer_settings* settings, int32_t sample_rate) {
+  return bind_settings(c, __func__, settings, 1, sample_rate);
+}
+
+ART_API int art_dsp_settings_bind_classes(art_ctx* c, const art_spatializer_settings* settings, int32_t class_count,
+                                          int32_t sample_rate) {
+  return bind_settings(c, __func__, settings, class_count, sample_rate);
+}
+
+// ---------------------------------------------------------------------------- the class map
+ART_API int art_dsp_target_classes_set(art_ctx* c, const uint8_t* cls, int32_t count) {
+  if (!c) return ART_E_INVALID;
+  if (count < 0 || count > kMaxTargets || (count > 0 && !cls))
+    return fail(c, ART_E_INVALID, "%s: count outside [0, %d] or a NULL map", __func__, kMaxTargets);
+  c->tick.target_class.assign(cls, cls + count);
+  return ART_OK;
+}
+
+ART_API int art_dsp_target_classes_get(art_ctx* c, uint8_t* out, int32_t cap) {
+  if (!c || cap < 0 || (cap > 0 && !out)) return ART_E_INVALID;
+  const std::vector<uint8_t>& m = c->tick.target_class;
+  for (int32_t i = 0; i < cap && (size_t)i < m.size(); ++i) out[i] = m[(size_t)i];
+  return (int)m.size();
 }
 
 // What the listener mix asks of its buffers (dsp_mix_kernel's 8-B buffer operations with 32-bit byte
@@ -183,6 +239,17 @@ static int tick_params(art_ctx* c, const char* fn, const void* d_block, uint32_t
   Device& dv = c->devs[0];
   if (dv.sc.T != f.T || !dv.sc.targets) return fail(c, ART_E_STATE, "%s: the bound scene's targets are not the frame's", fn);
   if ((long long)fan_count * f.T > 0x7fffffffLL) return fail(c, ART_E_UNSUPPORTED, "%s: more than 2^31 - 1 sources", fn);
+  // one class and no map: dsp_tick_params_kernel on that class, as before there were classes
+  const std::vector<uint8_t>& cls = c->tick.target_class;
+  const bool classes = c->tick.class_count > 1 || !cls.empty();
+  if (!cls.empty()) {
+    if ((int)cls.size() != f.T)
+      return fail(c, ART_E_STATE, "%s: the class map has %d entries, the bound frame %d targets (art_dsp_target_classes_follow)",
+                  fn, (int)cls.size(), f.T);
+    for (int t = 0; t < f.T; ++t)
+      if (cls[(size_t)t] >= c->tick.class_count)
+        return fail(c, ART_E_STATE, "%s: target %d names class %d, %d are bound", fn, t, (int)cls[(size_t)t], c->tick.class_count);
+  }
   if (mix && mix->frames > 0) {
     const char* why = nullptr;
     if (int rc = mix_limits(mix->d_dry, mix->d_mix, fan_count, f.T, mix->frames, why)) return fail(c, rc, "%s: %s", fn, why);
@@ -207,7 +274,18 @@ static int tick_params(art_ctx* c, const char* fn, const void* d_block, uint32_t
   a.sr = (float)c->tick.sample_rate;
   int rc = scene_reader_begin(c, dv, f, st);
   if (rc) return rc;
-  launch_dsp_tick_params(a, st);
+  if (classes) {
+    DspTickClassArgs b{};
+    b.block = a.block; b.stride = a.stride; b.settings_off = a.settings_off;
+    b.T = f.T; b.fan_count = fan_count;
+    b.listeners = a.listeners; b.targets = a.targets; b.volume = a.volume; b.out = a.out;
+    b.table = c->tick.d_table;
+    b.sr = a.sr;
+    if (!cls.empty()) std::memcpy(b.cls, cls.data(), cls.size());  // empty: all class 0
+    launch_dsp_tick_params_classes(b, st);
+  } else {
+    launch_dsp_tick_params(a, st);
+  }
   HIP_TRY(c, hipGetLastError());
   count_out = a.count;
   return scene_reader_end(c, dv, st);
@@ -298,6 +376,34 @@ static bool follow_map_ok(const int32_t* target_src, int32_t T_new, int32_t T_ol
   for (int32_t t = 0; t < T_new; ++t)
     if (target_src[t] < -1 || target_src[t] >= T_old) return false;
   return true;
+}
+
+ART_API int art_dsp_target_classes_follow(art_ctx* c, const int32_t* target_src, int32_t target_count_new,
+                                          int32_t target_count_old, uint8_t new_class) {
+  if (!c) return ART_E_INVALID;
+  if (target_count_new < 0 || target_count_old < 0) return fail(c, ART_E_INVALID, "%s: negative count", __func__);
+  if (!target_src) {  // the store's follow map: the caller's counts must be the store's
+    const TargetStore& t = c->targets;
+    if (target_count_new != t.synced || target_count_old != t.base_count)
+      return fail(c, ART_E_INVALID, "%s: target counts %d <- %d are not the store's (synced %d, follow base %d)", __func__,
+                  target_count_new, target_count_old, t.synced, t.base_count);
+    target_src = t.follow.data();
+  }
+  if (target_count_new > kMaxTargets || target_count_old > kMaxTargets)
+    return fail(c, ART_E_UNSUPPORTED, "%s: more than %d targets", __func__, kMaxTargets);
+  std::vector<uint8_t>& m = c->tick.target_class;
+  if (!m.empty() && (int32_t)m.size() != target_count_old)
+    return fail(c, ART_E_INVALID, "%s: the class map has %d entries, target_count_old is %d", __func__, (int)m.size(),
+                target_count_old);
+  if (target_count_new > 0 && !follow_map_ok(target_src, target_count_new, target_count_old))
+    return fail(c, ART_E_INVALID, "%s: a target_src entry lies outside [-1, %d)", __func__, target_count_old);
+  std::vector<uint8_t> next((size_t)target_count_new);
+  for (int32_t t = 0; t < target_count_new; ++t) {
+    const int32_t to = target_src[t];
+    next[(size_t)t] = to < 0 ? new_class : m.empty() ? (uint8_t)0 : m[(size_t)to];  // an empty map is all zeros
+  }
+  m.swap(next);
+  return ART_OK;
 }
 
 ART_API int art_dsp_sources_follow_host(const int32_t* target_src, int32_t target_count_new, int32_t target_count_old,

@@ -179,6 +179,25 @@ struct DspTickArgs {
   float sr;
 };
 void launch_dsp_tick_params(const DspTickArgs& a, hipStream_t st);
+// The same step with spatializer settings per target (art_dsp_settings_bind_classes): source s = f * T + t
+// is evaluated with settings[cls ? cls[t] : 0]. The host twin checks every class's curves, every map
+// entry and every fan's settings pointer before it writes (ART_E_INVALID).
+constexpr int kMaxSettingsClasses = 256;
+int dsp_tick_params_classes_host(const art_spatializer_settings* settings, int class_count, int sample_rate,
+                                 const art_listener* listeners, const art_fan* fans, int fan_count, const float* targets,
+                                 int T, const uint8_t* cls, const float* volume, art_dsp_source_params* out);
+struct DspTickClassArgs {
+  const uint8_t* block; uint32_t stride, settings_off;
+  int T, fan_count;
+  const art_listener* listeners;          // [fan_count]
+  const float* targets;                   // float3[T]: the bound scene's
+  const float* volume;                    // [fan_count * T] or nullptr
+  art_dsp_source_params* out;             // [fan_count * T]
+  const art_spatializer_settings* table;  // device: the bound classes, their curves in the same allocation
+  float sr;
+  uint8_t cls[kMaxTargets];               // [T], each below the bound class count (in the argument block)
+};
+void launch_dsp_tick_params_classes(const DspTickClassArgs& a, hipStream_t st);
 // The listener mix (art_dsp_mix_*): source s = f * T + t runs its chain over dry[t] (float[T][frames][2],
 // only read); mix[f] (float[fan_count][frames][2]) = the fan's T results summed in ascending t.
 // The device form needs 8-B aligned dry / mix and T * frames * 8, fan_count * frames * 8 < 2^31.

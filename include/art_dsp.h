@@ -154,6 +154,59 @@ ART_API int art_dsp_tick_device(art_ctx* ctx, const void* d_block, uint32_t out_
         const art_listener* d_listeners, const float* d_volume, float* d_data, art_dsp_state* d_state,
         int32_t frames, art_dsp_source_params* d_params, void* stream);
 
+/* ---- settings per target (ABI 3.15): a table of settings classes and a class map --------------- */
+
+/* Every AudioSpatializer carries its own settings (AudioSpatializer.cs:10-11, baked in Awake :38-39,
+ * beside its volumeMultiplier :18). A settings class is one art_spatializer_settings; a context binds a
+ * table of K classes (1 <= K <= 256) and each target of the scene names one class through the class
+ * map, uint8 class_of[T]. Source s = f*T + t is evaluated with settings[class_of[t]]; the listener
+ * step, the target position, the volume, the sample rate (one per table) and the record are as above.
+ * The contract, literally:
+ *   out[f*T + t] = what art_dsp_tick_params_host writes for that source when it is given
+ *                  settings[class_of[t]] as its single settings
+ *
+ * Host twin, context-free: settings = art_spatializer_settings[class_count]; target_class =
+ * uint8[target_count], or NULL = every target is class 0; the other arguments as
+ * art_dsp_tick_params_host. ART_E_INVALID, with nothing written, when class_count is outside [1, 256],
+ * when any class has a curve that is not valid (both curves of every class, used or not, as for the
+ * device bind), or when a map entry is >= class_count. */
+ART_API int art_dsp_tick_params_classes_host(const art_spatializer_settings* settings, int32_t class_count,
+        int32_t sample_rate, const art_listener* listeners, const art_fan* fans, int32_t fan_count,
+        const float* target_positions, int32_t target_count,
+        const uint8_t* target_class /* uint8[target_count] or NULL = all class 0 */,
+        const float* volume, art_dsp_source_params* out);
+
+/* Copy the class_count records and upload the table and all 2 * class_count curves (each with its own
+ * sample_count and length) to the context's first device, as one packed image in one copy. Ordered
+ * and synchronous like art_dsp_settings_bind: it waits for a pending reader before it replaces
+ * anything. It replaces any earlier bind of either kind; art_dsp_settings_bind is the bind of one
+ * class. A bind does not touch the class map. ART_E_INVALID for class_count outside [1, 256] or a
+ * curve that is not valid, ART_E_STATE while a frame is in flight, ART_E_UNSUPPORTED on the CPU
+ * backend. */
+ART_API int art_dsp_settings_bind_classes(art_ctx* ctx, const art_spatializer_settings* settings,
+        int32_t class_count, int32_t sample_rate);
+
+/* The class map: host state of the context. count in [0, 256]; 0 is the initial state and means
+ * "every target is class 0". Pure host calls: no synchronisation, and they work on the CPU backend
+ * (as art_target_follow_map does). _get copies min(cap, count) entries and returns the count.
+ * ART_E_INVALID for a NULL context, a count outside [0, 256], cap < 0, or a NULL array with a
+ * positive count / cap. Entries are checked against the bound class count by the tick, not here. */
+ART_API int art_dsp_target_classes_set(art_ctx* ctx, const uint8_t* cls, int32_t count);
+ART_API int art_dsp_target_classes_get(art_ctx* ctx, uint8_t* out, int32_t cap);
+
+/* The tick under classes. art_dsp_tick_params_device, art_dsp_tick_device and
+ * art_dsp_tick_mix_device keep their signatures. With one class bound and an empty map they do what
+ * they always did (the same kernel, the same arguments). With more classes or a non-empty map they
+ * use the table and the map: still one launch for the parameter step, no extra host work, and the
+ * map travels in the kernel's argument block (it is read before the call returns and is
+ * stream-ordered with the launch: a later art_dsp_target_classes_set does not reach a tick already
+ * enqueued). Checked before anything is enqueued:
+ *   ART_E_STATE  the map is not empty and its length differs from the bound frame's target count
+ *                (the caller's check that it followed a count change);
+ *   ART_E_STATE  a map entry is >= the bound class count.
+ * A churn that keeps the target count (a remove plus an add) cannot be detected by length: moving
+ * the map after target churn is the caller's duty, exactly as for d_state (below). */
+
 /* ---- listener mix (ABI 3.6): one dry buffer per target in, one mix per fan out ------------------ */
 
 /* A server with one listener per fan: the scene's T audio targets are shared by every fan, so there
@@ -241,6 +294,21 @@ ART_API int art_dsp_sources_follow_device(art_ctx* ctx,
         int32_t fan_count_new, int32_t fan_count_old,
         const art_dsp_state* d_state_old, const float* d_volume_old,
         art_dsp_state* d_state_new, float* d_volume_new, float new_volume, void* stream);
+
+/* The class map (ABI 3.15) follows the targets with the semantics of art_dsp_sources_follow_host for
+ * one fan: new[t] = old[target_src[t]] when 0 <= target_src[t] < target_count_old, new_class when it
+ * is -1. Host only (works on the CPU backend, no synchronisation). target_src NULL = the store's
+ * follow map, with the checks of art_dsp_sources_follow_device: the counts must equal
+ * art_target_synced_count and the follow map's base count, else ART_E_INVALID. target_count_old must
+ * equal the map's current length unless the map is empty; an empty map is treated as all zeros
+ * (and becomes a map of target_count_new entries). ART_E_INVALID also for a negative count or a
+ * target_src entry outside [-1, target_count_old); ART_E_UNSUPPORTED for a count above 256. Nothing
+ * changes on an error. Call it before art_target_follow_mark, like the move of d_state: the order
+ * after target churn is art_targets_sync, art_dsp_target_classes_follow,
+ * art_dsp_sources_follow_device, art_target_follow_mark. */
+ART_API int art_dsp_target_classes_follow(art_ctx* ctx,
+        const int32_t* target_src /* host, or NULL = the store's follow map */,
+        int32_t target_count_new, int32_t target_count_old, uint8_t new_class);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@
 the muffle cell lists and the target syncs' kernels a third, csrc/art_cells.hip: profiles/targets_resize_spill.txt,
 the BVH build, refit and relabel kernels a fourth, csrc/art_bvh.hip: profiles/colliders_resize_spill.txt,
 the per-sample DSP, the tick, the mix and dsp_sources_follow_kernel a fifth, csrc/art_dsp.hip:
-profiles/sources_follow_spill.txt.)
+profiles/sources_follow_spill.txt, with dsp_tick_params_classes_kernel profiles/tick_classes_spill.txt.)
 
 For every kernel: its VGPR count, scratch, LDS, occupancy and code length, and for each spill slot the stores and reloads
 with the loop they sit in (the compiler's "Loop Header" / "in Loop" block annotations). A spill

@@ -4,6 +4,7 @@ every source of a config's frame (fans x targets) spatialized from the frame's o
 `frames` samples per buffer at 48 kHz. GPU box only.
     python3 tools/tick_run.py [config] [steps] [--frames N]
     python3 tools/tick_run.py --mix-batch FANS [steps] [--frames N] [--targets T]
+    python3 tools/tick_run.py --classes K[,K...] [steps] [--shapes FANSxT[,FANSxT...]]
 Per tick, on torch's stream:
   (a) device tick   art_launch_device + art_dsp_tick_device (no host synchronisation)
   (b) host params   art_launch_device, D2H copy of the settings sections (pinned), art_dsp_tick_params_host,
@@ -16,7 +17,10 @@ and the parameter step alone (art_dsp_tick_params_device back to back: an upper 
 dsp_tick_params_kernel's own time; a rocprofv3 --kernel-trace of this tool gives the kernel's).
 --mix-batch times art_dsp_mix_device alone (device events) on FANS fans of random sources beside
 art_dsp_process_device on the same FANS * T sources, and prints the algorithmic HBM bytes of both
-(a rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass of this mode gives the measured ones)."""
+(a rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass of this mode gives the measured ones).
+--classes times art_dsp_tick_params_device alone (device events) under a single bind (K = 1) and under K
+settings classes (art_dsp_settings_bind_classes), on synthetic blocks of the given shapes (default: 256 fans
+x 4 targets and 4096 x 64): profiles/tick_classes.txt."""
 import ctypes as C
 import os
 import sys
@@ -122,11 +126,113 @@ def mix_batch(F, T, frames, steps):
     ctx.close()
 
 
+def take_str(argv, flag, default):
+    if flag not in argv:
+        return default
+    at = argv.index(flag)
+    v = argv[at + 1]
+    del argv[at:at + 2]
+    return v
+
+
+def classes_run(Ks, shapes, steps):
+    """The parameter step alone under a single bind (K = 1: art_dsp_settings_bind, no class map) and under
+    K settings classes (art_dsp_settings_bind_classes, target t in class t % K), on a synthetic block of
+    random settings records over the tiny scene with T targets. Before timing, the device parameters are
+    compared with the host twin's. Device events: around every single call, and around `steps` calls
+    back to back (per call). Every (shape, K) is timed in two rounds, K alternating within a round."""
+    rng = np.random.default_rng(15)
+    dev = torch.device("cuda", 0)
+    sp = torch.cuda.current_stream().cuda_stream
+
+    def one_class():
+        u = lambda a, b: float(rng.uniform(a, b))  # noqa: E731
+        return SpatializerSettings(
+            pan_strength=u(0.1, 1), rear_attenuation_strength=u(0.1, 1), distance_based_panning=bool(rng.random() < 0.5),
+            max_pan_distance=u(1, 10), distance_based_rear_attenuation=bool(rng.random() < 0.5),
+            max_rear_attenuation_distance=u(1, 30), max_elevation_effect_distance=u(1, 20),
+            muffle_curve=rng.random(int(rng.integers(2, 60))).astype(np.float32),
+            reverb_volume_curve=rng.random(int(rng.integers(2, 60))).astype(np.float32))
+
+    classes = [SpatializerSettings()] + [one_class() for _ in range(max(Ks) - 1)]
+    for F, T in shapes:
+        scene, org, params = art.synth(art.CONFIGS[2], S=1, R=64, C_scale=0.01)
+        extra = rng.uniform(-20, 20, (max(0, T - scene.T), 3)).astype(np.float32)
+        scene = art.Scene(dirs=scene.dirs, targets=np.ascontiguousarray(np.concatenate([scene.targets, extra])[:T]),
+                          spheres=scene.spheres, aabbs=scene.aabbs)
+        ctx = art.Context(1)
+        frame = art.Frame(scene, params, org, art.FanOutputs(1, 64, params.max_hits_per_ray, T, 1))
+        ctx.bind(frame)
+        lay = art.fan_layout(frame)
+        listeners = np.zeros(F, abi.LISTENER)
+        listeners["position"] = rng.uniform(-30, 30, (F, 3))
+        q = rng.standard_normal((F, 4))
+        listeners["rotation"] = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
+        fs = np.zeros((F, T), abi.SETTINGS)
+        fs["muffle_strength"] = np.where(rng.random((F, T)) < 0.3, 0.0, rng.random((F, T)))
+        fs["reverb_strength"] = rng.random((F, T))
+        fs["reverb_volume"] = rng.random((F, T))
+        fs["perceived_position"] = rng.uniform(-30, 30, (F, T, 3))
+        block = np.zeros((F, lay["stride"]), np.uint8)
+        block[:, lay["settings_off"]:lay["settings_off"] + T * 24] = fs.view(np.uint8).reshape(F, T * 24)
+        d_blk = torch.from_numpy(block.reshape(-1)).to(dev)
+        d_ls = torch.from_numpy(listeners.view(np.uint8).copy()).to(dev)
+        d_par = torch.zeros(F * T * 32, dtype=torch.uint8, device=dev)
+        print(f"classes: {F} fans x {T} targets = {F * T} sources", flush=True)
+
+        def call():
+            art.dsp.tick_params_device(ctx, d_blk, F, d_ls, d_par, None, 0, sp)
+
+        def setup(K):
+            if K == 1:
+                art.dsp.bind_settings(ctx, classes[0], SAMPLE_RATE)
+                return art.dsp.tick_params_host(classes[0], listeners, fs, scene.targets, None, SAMPLE_RATE)
+            cls = (np.arange(T) % K).astype(np.uint8)
+            art.dsp.bind_settings_classes(ctx, classes[:K], SAMPLE_RATE)
+            art.dsp.set_target_classes(ctx, cls)
+            return art.dsp.tick_params_classes_host(classes[:K], listeners, fs, scene.targets, cls, None, SAMPLE_RATE)
+
+        for rnd in range(2):
+            for K in Ks:
+                want = setup(K)
+                for _ in range(5):
+                    call()
+                torch.cuda.synchronize()
+                same = d_par.cpu().numpy().tobytes() == want.tobytes()
+                ts = []
+                for _ in range(steps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    call()
+                    e1.record()
+                    e1.synchronize()
+                    ts.append(e0.elapsed_time(e1) * 1e3)
+                ts.sort()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(steps):
+                    call()
+                e1.record()
+                e1.synchronize()
+                what = "single bind" if K == 1 else f"K = {K} classes"
+                print(f"classes: {F} x {T}, round {rnd}, {what}: params_step_us min {ts[0]:.2f} median {ts[len(ts) // 2]:.2f} "
+                      f"(events around one call), {e0.elapsed_time(e1) * 1e3 / steps:.2f} per call over {steps} calls back to "
+                      f"back; equals the host twin: {same}", flush=True)
+                if K > 1:
+                    art.dsp.set_target_classes(ctx, [])
+        ctx.close()
+
+
 def main():
     argv = sys.argv[1:]
     frames = take(argv, "--frames", 1024)
+    classes = take_str(argv, "--classes", "")
+    shapes = take_str(argv, "--shapes", "256x4,4096x64")
     targets = take(argv, "--targets", 4)
     batch = take(argv, "--mix-batch", 0)
+    if classes:
+        return classes_run([int(k) for k in classes.split(",")], [tuple(int(v) for v in s.split("x")) for s in shapes.split(",")],
+                           int(argv[0]) if argv else 200)
     if batch:
         return mix_batch(batch, targets, frames, int(argv[0]) if argv else 20)
     cfg = art.CONFIGS[int(argv[0]) if len(argv) > 0 else 2]
